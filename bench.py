@@ -3,7 +3,12 @@
 "GiB/s uncompressed in (deflate) + out (inflate), Silesia 64KiB blocks").
 
   python bench.py --gpus N --steps K --warmup W [--config corpus|c2|c5] [--blocks B] [--corpus-jobs J]
-                  [--no-c2] [--no-c5] [--no-inflate] [--no-api] [--no-cpu-baseline]
+                  [--dump-outputs DIR] [--full [--no-c2] [--no-c5] [--no-inflate] [--no-api] [--no-cpu-baseline]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...);
+with --dump-outputs DIR it also writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a
+seeded sample of the rows where the whole output is too large).  Everything else below -- the round-trip and zlib
+checks, the per-class rates, the roofline and copy peak, the CPU baselines and the side objects -- runs with --full.
 
 config corpus (default; BASELINE.json configs[2], the metric's own kind of data): the real-data corpus --
   Silesia from $SILESIA_DIR (sha256-checked against the pins of the reference's oct/silesia-*.source) or
@@ -12,8 +17,8 @@ config corpus (default; BASELINE.json configs[2], the metric's own kind of data)
   table per block built on the device (function code COMPRESS_DHTGEN: LZ77 kernel -> dhtgen kernel ->
   entropy kernel).  Every rank owns its own J jobs (independent units, no data-path collective: weak
   scaling); the only collectives are the barrier and the reductions of {bytes, elapsed}.  Rank 0 prints
-  ONE JSON line with `roofline` and `cpu_baseline` (zlib -1 on the same chunks, the reference's software
-  path) and, at N = 1, outside the timed region:
+  ONE JSON line; with --full it holds `roofline` and `cpu_baseline` (zlib -1 on the same chunks, the
+  reference's software path) and, at N = 1, outside the timed region:
     "inflate_zlib6", "inflate_stream"  the inflate engine on zlib -6 streams of the corpus chunks (batch)
                and on ONE long zlib -6 stream (block-boundary speculation, BASELINE configs[3])
     "api"      the reference's own API (nx_compress2 / nx_uncompress / inflate() in steps) on host buffers
@@ -26,8 +31,8 @@ config c5: 10 GiB of mixed-entropy 64 KiB blocks (index mod 4: zeros / 33-symbol
   compress (FHT; what does not shrink is stored through the WRAP function code, inside the timed region)
   + decompress + compare on the device.
 
-Inside the timed region: the engine launches only.  Outside: data generation, zlib verification of
-a sample, the CPU baselines (with the oracle parity check).
+Inside the timed region: the engine launches only.  Outside: data generation and, with --full, zlib
+verification of a sample, the CPU baselines (with the oracle parity check).
 """
 import argparse
 import ctypes as C
@@ -102,6 +107,47 @@ def dev_equal(torch, a, b, rows=32768):
         if not torch.equal(a[i:i + rows], b[i:i + rows]):
             return False
     return True
+
+
+DUMP_LIMIT = 64 * 10 ** 6      # --dump-outputs: bytes in all
+DUMP_ROWS = 128                # ... jobs whose output bytes are written, a seeded sample
+DUMP_SEED = 20250101
+
+
+def dump_sample(n):
+    """the jobs --dump-outputs writes the bytes of: the same DUMP_ROWS of n in every run"""
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_ROWS), replace=False))
+
+
+def dump_results(res, idx, room):
+    """the completion records of every job as (n, 8) float64 (cc, tpbc, ..., sfbt), or of the sampled jobs when all of
+    them do not fit in `room` bytes"""
+    names = importlib.import_module("power-gzip_amd").RESULT_DTYPE.names
+    full = np.stack([res[f].astype(np.float64) for f in names], axis=1)
+    return {"results": full} if full.nbytes <= room else {"results_sample": full[idx]}
+
+
+def dump_deflate(torch, dst, res, n):
+    """what a caller of the batched compress receives: the completion records, and the output bytes of a seeded sample of
+    the jobs as float32 rows of the target stride, zero from the job's byte count (tpbc) on"""
+    idx = dump_sample(n)
+    rows = dst[torch.from_numpy(idx).to(dst.device)].cpu().numpy()
+    tpbc = res["tpbc"][idx].astype(np.int64)
+    comp = np.where(np.arange(rows.shape[1])[None, :] < tpbc[:, None], rows, 0).astype(np.float32)
+    out = {"sample_index": idx.astype(np.float64), "compressed": comp}
+    out.update(dump_results(res, idx, DUMP_LIMIT - comp.nbytes - idx.nbytes))
+    return out
+
+
+def write_dump(directory, arrays):
+    """--dump-outputs: every array as directory/<name>.npy"""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes, more than %d" % (total, DUMP_LIMIT))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def shard(nblocks_per_rank, rank, world):
@@ -408,7 +454,6 @@ def roofline(u_bytes, c_bytes, stage_ms, launches, traffic, kernel, peak_measure
 
 def run_corpus(torch, dist, args, rank, world, dev, distributed, pkg, eng):
     """The headline: real data (the metric's corpus), exact dynamic-Huffman table per block (BASELINE configs[2])."""
-    import zlib
     import corpus
     name, blocks, report = corpus.load(BLOCK)
     uniq = len(blocks)
@@ -434,7 +479,10 @@ def run_corpus(torch, dist, args, rank, world, dev, distributed, pkg, eng):
     if distributed:
         dist.barrier()
     torch.cuda.synchronize(dev)
-    eng.L.nxz_ctx_stage_timing(eng.ctx, 1)                 # HIP events on the launch stream around every kernel
+    # --full: HIP events on the launch stream around every kernel, for the roofline's stage times.  A plain run leaves them
+    # off: its timed steps are the engine's launches and nothing else
+    if args.full:
+        eng.L.nxz_ctx_stage_timing(eng.ctx, 1)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -443,27 +491,63 @@ def run_corpus(torch, dist, args, rank, world, dev, distributed, pkg, eng):
         dist.barrier()
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
-    eng.L.nxz_ctx_stage_timing(eng.ctx, 0)
-    st, launches = stage_times(eng)
-    st = [x / args.steps for x in st]
-    launches //= args.steps
+    if args.full:
+        eng.L.nxz_ctx_stage_timing(eng.ctx, 0)
+        st, launches = stage_times(eng)
+        st = [x / args.steps for x in st]
+        launches //= args.steps
 
     r = eng.results_to_host(res)
     if not ((r["cc"] == 0) | (r["cc"] == 64)).all():
         raise SystemExit("corpus: engine reported errors %s" % np.unique(r["cc"]))
+    if args.dump_outputs and rank == 0:
+        write_dump(args.dump_outputs, dump_deflate(torch, dst, r, n))
     # a block that did not shrink (cc 64) leaves the library as a stored block, 5 bytes of header (lib/nx_deflate.c:1274-1282)
     out_bytes = np.where(r["cc"] == 64, lens.astype(np.int64) + 5, r["tpbc"].astype(np.int64))
     u_bytes, c_bytes = float(lens.astype(np.float64).sum()), float(out_bytes.astype(np.float64).sum())
-    # every output inflates back (on the device, full size) -- on every rank
-    back = torch.zeros((n, BLOCK), dtype=torch.uint8, device=dev)
-    jobs2 = eng.jobs_strided(dst, STRIDE_OUT, r["tpbc"].astype(np.uint32), back, BLOCK, BLOCK)
-    r2 = eng.results_to_host(eng.decompress(jobs2, n))
-    if not (bool((r2["cc"] == 0).all()) and bool((r2["tpbc"] == lens).all()) and dev_equal(torch, back, src)):
-        raise SystemExit("corpus: ROUND TRIP FAILURE on rank %d (inflate of the deflate output != source)" % rank)
-    del back
+    if args.full:
+        # every output inflates back (on the device, full size) -- on every rank
+        back = torch.zeros((n, BLOCK), dtype=torch.uint8, device=dev)
+        jobs2 = eng.jobs_strided(dst, STRIDE_OUT, r["tpbc"].astype(np.uint32), back, BLOCK, BLOCK)
+        r2 = eng.results_to_host(eng.decompress(jobs2, n))
+        if not (bool((r2["cc"] == 0).all()) and bool((r2["tpbc"] == lens).all()) and dev_equal(torch, back, src)):
+            raise SystemExit("corpus: ROUND TRIP FAILURE on rank %d (inflate of the deflate output != source)" % rank)
+        del back
     tot_u, tot_c, wall_max = reduce_totals(torch, dist, dev, u_bytes, c_bytes, wall, distributed)
     if rank != 0:
         return
+    line = {
+        "metric": "GiB/s uncompressed in (deflate), real-data corpus in 64 KiB blocks, exact dynamic-Huffman table per block",
+        "value": round(tot_u * args.steps / wall_max / 2.0 ** 30, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(wall_max / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8",
+        "data": "Silesia ($SILESIA_DIR, sha256-checked)" if name == "silesia" else
+                "real files of this image (recorded fallback corpus: Silesia is not on the box), replicated",
+        "corpus_skipped": report.get("skipped", []) if isinstance(report, dict) else [],
+        "data_note": "the %d unique blocks (%.0f MB) are replicated %d x: the SOURCE set fits the 256 MB Infinity Cache, which does not matter at "
+                     "1-2 %% of the HBM roof (the kernels are bound by instruction issue, roofline.what_binds)" % (uniq, uniq * BLOCK / 1e6, rep),
+        "config": {"workload": "BASELINE configs[2]: dynamic-Huffman deflate (COMPRESS_DHTGEN: LZ77 + histogram, dhtgen on the device, "
+                               "entropy) of the %s corpus cut at 64 KiB, %d jobs per GPU (%d unique blocks), device resident" % (name, n, uniq),
+                   "corpus": name, "corpus_files": report, "unique_blocks": uniq, "jobs_per_gpu": n, "block_bytes": BLOCK,
+                   "ratio": round(float(lens_u.astype(np.float64).sum()) / float(out_bytes[:uniq].astype(np.float64).sum()), 4),
+                   "parallelism": "shard%d" % world},
+    }
+    if args.full:
+        # (the headline's buffers change hands, so that the legs after it can free them)
+        bufs = {"src": src, "dst": dst, "jobs": jobs, "res": res}
+        del src, dst, jobs, res
+        corpus_full(torch, dist, args, world, dev, pkg, eng, line, blocks, rep, bufs, r, out_bytes, u_bytes, c_bytes, st, launches)
+    print(json.dumps(line), flush=True)
+
+
+def corpus_full(torch, dist, args, world, dev, pkg, eng, line, blocks, rep, bufs, r, out_bytes, u_bytes, c_bytes, st, launches):
+    """--full, after the headline of the corpus config (rank 0): zlib checks and ratios, the rate by class, the roofline, the
+    CPU baseline and, at N = 1, the inflate / api / c2 / c5 legs -- all into `line`.  `bufs`: the headline's src, dst, jobs
+    and res, freed before the legs that size themselves by the device's free memory"""
+    import zlib
+    import corpus
+    uniq, n, name = len(blocks), len(blocks) * rep, line["config"]["corpus"]
+    src, dst, jobs, res = bufs.pop("src"), bufs.pop("dst"), bufs.pop("jobs"), bufs.pop("res")
     out_u = dst[:uniq].cpu().numpy()
     raw = [b for _, _, b in blocks]
     verify_sample(raw, out_u, r["tpbc"], k=uniq if uniq <= 400 else 400)      # ... and a sample through zlib
@@ -504,27 +588,13 @@ def run_corpus(torch, dist, args, rank, world, dev, distributed, pkg, eng):
         silesia = {"value": round(tot_b / secs, 1), "unit": "GiB/s", "how": "12 files x published size / rate of the stand-in class (time-weighted)",
                    "class_of_file": corpus.SILESIA_AS_FALLBACK_CLASS}
     peak_m = copy_peak_gbs(torch, dev, eng)
-    line = {
-        "metric": "GiB/s uncompressed in (deflate), real-data corpus in 64 KiB blocks, exact dynamic-Huffman table per block",
-        "value": round(tot_u * args.steps / wall_max / 2.0 ** 30, 3), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(wall_max / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8",
-        "data": "Silesia ($SILESIA_DIR, sha256-checked)" if name == "silesia" else
-                "real files of this image (recorded fallback corpus: Silesia is not on the box), replicated",
-        "corpus_skipped": report.get("skipped", []) if isinstance(report, dict) else [],
-        "data_note": "the %d unique blocks (%.0f MB) are replicated %d x: the SOURCE set fits the 256 MB Infinity Cache, which does not matter at "
-                     "1-2 %% of the HBM roof (the kernels are bound by instruction issue, roofline.what_binds)" % (uniq, uniq * BLOCK / 1e6, rep),
-        "config": {"workload": "BASELINE configs[2]: dynamic-Huffman deflate (COMPRESS_DHTGEN: LZ77 + histogram, dhtgen on the device, "
-                               "entropy) of the %s corpus cut at 64 KiB, %d jobs per GPU (%d unique blocks), device resident" % (name, n, uniq),
-                   "corpus": name, "corpus_files": report, "unique_blocks": uniq, "jobs_per_gpu": n, "block_bytes": BLOCK,
-                   "ratio": round(tot[0] / tot[1], 4), "zlib1_ratio": round(tot[0] / tot[2], 4), "ratio_vs_zlib1": round(tot[2] / tot[1], 4),
-                   "min_class_vs_zlib1": min(v["vs_zlib1"] for v in classes.values()),
-                   "min_class_GiB_s": min((v["GiB_s"] for v in classes.values() if "GiB_s" in v), default=None),
-                   "silesia_weighted_GiB_s": silesia, "classes": classes,
-                   "roundtrip_bit_exact": True, "zlib_inflated_sample": min(uniq, 400), "parallelism": "shard%d" % world},
-        "roofline": roofline(u_bytes, c_bytes, st, launches, pmc_traffic(n, "dhtgen"),
-                             "nxzl77::lz77_kernel<true, false, false> (dominant) + nxzd::dhtgen_kernel + nxze::encode_kernel<true, false>", peak_m),
-    }
+    line["config"].update({"ratio": round(tot[0] / tot[1], 4), "zlib1_ratio": round(tot[0] / tot[2], 4), "ratio_vs_zlib1": round(tot[2] / tot[1], 4),
+                           "min_class_vs_zlib1": min(v["vs_zlib1"] for v in classes.values()),
+                           "min_class_GiB_s": min((v["GiB_s"] for v in classes.values() if "GiB_s" in v), default=None),
+                           "silesia_weighted_GiB_s": silesia, "classes": classes,
+                           "roundtrip_bit_exact": True, "zlib_inflated_sample": min(uniq, 400)})
+    line["roofline"] = roofline(u_bytes, c_bytes, st, launches, pmc_traffic(n, "dhtgen"),
+                                "nxzl77::lz77_kernel<true, false, false> (dominant) + nxzd::dhtgen_kernel + nxze::encode_kernel<true, false>", peak_m)
     if world > 1:
         # a scaling line: the legs that belong to one GPU's report are left out, and the line says so
         line["legs_skipped"] = ["cpu_baseline", "inflate_zlib6", "inflate_stream", "api", "c2", "c5"]
@@ -557,7 +627,6 @@ def run_corpus(torch, dist, args, rank, world, dev, distributed, pkg, eng):
         if not args.no_c5:
             torch.cuda.empty_cache()
             line["c5"] = c5_measure(torch, dist, args, 0, 1, dev, False, pkg, eng, 163840, max(2, args.steps // 2), 1)
-    print(json.dumps(line), flush=True)
 
 
 def api_leg(raw, args, mib=256, nthreads=16, raw_r04=None):
@@ -944,8 +1013,9 @@ def c5_prepare(torch, eng, pkg, src):
                   "flag": flag, "c_bytes": c_bytes, "keep": (jobs, res, jw, jd, ju, resw, resd)}
 
 
-def c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, total, steps, warmup):
-    """BASELINE configs[4]: 10 GiB mixed entropy, contiguous strong-scaled shards; the JSON line (rank 0) or None."""
+def c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, total, steps, warmup, dump=None):
+    """BASELINE configs[4]: 10 GiB mixed entropy, contiguous strong-scaled shards; the JSON line (rank 0) or None.
+    dump: the --dump-outputs directory of the last timed step's outputs (rank 0), if any."""
     lo, hi = shard_strong(total, rank, world)
     n = hi - lo
     src = gen_mixed(torch, dev, n, lo)
@@ -968,6 +1038,14 @@ def c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, total
     wall = time.perf_counter() - t0
     if int(flag.item()) != 0:
         raise SystemExit("ROUND TRIP FAILURE (c5): decompressed data != source on rank %d" % rank)
+    if dump and rank == 0:
+        # what the step hands on: the inflated blocks (a seeded sample) and the compress pass' completion records
+        idx = dump_sample(n)
+        back = info["back"][torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float32)
+        res = eng.results_to_host(info["keep"][1])
+        out = {"sample_index": idx.astype(np.float64), "decompressed": back}
+        out.update(dump_results(res, idx, DUMP_LIMIT - back.nbytes - idx.nbytes))
+        write_dump(dump, out)
     u_bytes = float(n) * BLOCK
     tot_u, tot_c, wall_max = reduce_totals(torch, dist, dev, u_bytes, info["c_bytes"], wall, distributed)
     if rank != 0:
@@ -983,10 +1061,11 @@ def c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, total
                                "shrink + decompress + compare, device resident" % (total, world),
                    "total_blocks": total, "block_bytes": BLOCK, "ratio": round(tot_u / tot_c, 4),
                    "stored_blocks_rank0": info["stored"], "roundtrip_bit_exact": True, "parallelism": "shard%d" % world},
-        "roofline": roof(2 * (tot_u + tot_c) * steps / wall_max / 1e9 / world, pmc_traffic(n, "c5"),
-                         "whole step (deflate + wrap + inflate kernels), wall clock, per GPU", copy_peak_gbs(torch, dev, eng)),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line["roofline"] = roof(2 * (tot_u + tot_c) * steps / wall_max / 1e9 / world, pmc_traffic(n, "c5"),
+                                "whole step (deflate + wrap + inflate kernels), wall clock, per GPU", copy_peak_gbs(torch, dev, eng))
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the reference's software path for the same step: zlib level 1 (fixed code) per block, stored when it does not
         # shrink, and zlib's inflate back -- a bounded sample of the same mix
         import zlib
@@ -1017,9 +1096,9 @@ def c2_default_blocks(torch, dev):
     return (1 << 20) if free_b > (212 << 30) else (1 << 18)
 
 
-def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, steps, warmup):
+def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, steps, warmup, dump=None):
     """BASELINE configs[1]: fixed-Huffman deflate of n synthetic 64 KiB blocks per GPU (weak scaling); the JSON
-    line (rank 0) or None."""
+    line (rank 0) or None.  dump: the --dump-outputs directory of the last timed step's outputs (rank 0), if any."""
     lo, hi = shard(n, rank, world)
     src = gen_blocks(torch, dev, n, lo)
     dst = torch.empty((n, STRIDE_OUT), dtype=torch.uint8, device=dev)
@@ -1038,7 +1117,10 @@ def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, st
         dist.barrier()
     torch.cuda.synchronize(dev)
 
-    eng.L.nxz_ctx_stage_timing(eng.ctx, 1)                 # HIP events on the launch stream around every kernel
+    # --full: HIP events on the launch stream around every kernel, for the roofline's stage times.  A plain run leaves them
+    # off: its timed steps are the engine's launches and nothing else
+    if args.full:
+        eng.L.nxz_ctx_stage_timing(eng.ctx, 1)
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
@@ -1047,21 +1129,24 @@ def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, st
         dist.barrier()
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t0
-    eng.L.nxz_ctx_stage_timing(eng.ctx, 0)
-    st, launches = stage_times(eng)
-    st = [x / steps for x in st]
-    launches //= steps
+    if args.full:
+        eng.L.nxz_ctx_stage_timing(eng.ctx, 0)
+        st, launches = stage_times(eng)
+        st = [x / steps for x in st]
+        launches //= steps
 
     res = results.cpu().numpy().view(pkg.RESULT_DTYPE)
     if not ((res["cc"] == 0) | (res["cc"] == 64)).all():
         raise SystemExit("engine reported errors: %s" % np.unique(res["cc"]))
-    peak_m = copy_peak_gbs(torch, dev, eng)
+    if dump and rank == 0:
+        write_dump(dump, dump_deflate(torch, dst, res, n))
+    peak_m = copy_peak_gbs(torch, dev, eng) if args.full else None
 
     # second leg of the metric (uncompressed bytes OUT of inflate), measured after the timed deflate
     # region on the same device-resident data: the inflate engine decodes the deflate engine's output
     # and the result is compared with the source on the device (bit-exact round trip at full size).
     inflate_info = None
-    if not args.no_inflate and rank == 0:
+    if args.full and not args.no_inflate and rank == 0:
         back = torch.empty((n, BLOCK), dtype=torch.uint8, device=dev)
         jobs2 = eng.jobs_strided(dst, STRIDE_OUT, res["tpbc"].astype(np.uint32), back, BLOCK, BLOCK)
         res2 = torch.empty(n * pkg.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
@@ -1106,10 +1191,11 @@ def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, st
     tot_u, tot_c, wall_max = reduce_totals(torch, dist, dev, u_bytes, c_bytes, wall, distributed)
     if rank != 0:
         return None
-    k = min(n, 48)
-    src_rows = [row.tobytes() for row in src[:k].cpu().numpy()]
-    out_rows = dst[:k].cpu().numpy()
-    verify_sample(src_rows, out_rows, res["tpbc"], k)
+    if args.full:
+        k = min(n, 48)
+        src_rows = [row.tobytes() for row in src[:k].cpu().numpy()]
+        out_rows = dst[:k].cpu().numpy()
+        verify_sample(src_rows, out_rows, res["tpbc"], k)
     value = tot_u * steps / wall_max / 2.0 ** 30
     line = {
         "metric": "GiB/s uncompressed in (deflate), fixed-Huffman level 1, synthetic 64 KiB blocks",
@@ -1120,12 +1206,13 @@ def c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n, st
                                "0x9E3779B97F4A7C15 ^ i: 33-symbol text, then makedata copies with per-block len_max / dist_max), device resident" % n,
                    "blocks_per_gpu": n, "block_bytes": BLOCK, "ratio": round(tot_u / tot_c, 4),
                    "parallelism": "shard%d" % world},
-        "roofline": roofline(u_bytes, c_bytes, st, launches, pmc_traffic(n, "fht"),
-                             "nxzl77::lz77_kernel<false, true, false> (one kernel: LZ77 + the fixed code)", peak_m, leg="fht"),
     }
+    if args.full:
+        line["roofline"] = roofline(u_bytes, c_bytes, st, launches, pmc_traffic(n, "fht"),
+                                    "nxzl77::lz77_kernel<false, true, false> (one kernel: LZ77 + the fixed code)", peak_m, leg="fht")
     if inflate_info:
         line["inflate"] = inflate_info
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sample = [row.tobytes() for row in src[:min(n, 2048)].cpu().numpy()]
         line["cpu_baseline"] = cpu_baseline_deflate(sample, "fixed", 10.0)
         line["cpu_baseline"]["parity_checked_blocks"] = oracle_parity(src_rows, out_rows, res["tpbc"], False)
@@ -1175,11 +1262,15 @@ def main():
                                                          "config 2^18); c5: total blocks (default 163840 = 10 GiB)")
     ap.add_argument("--corpus-jobs", type=int, default=262144, help="jobs per GPU of the corpus config (the corpus is replicated)")
     ap.add_argument("--class-jobs", type=int, default=0, help="corpus config: jobs of the per-class legs (0 = as many as the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-inflate", action="store_true", help="skip the inflate legs")
-    ap.add_argument("--no-api", action="store_true", help="skip the host-buffer API leg")
-    ap.add_argument("--no-c2", action="store_true", help="corpus config: skip the c2 side object")
-    ap.add_argument("--no-c5", action="store_true", help="corpus config: skip the c5 side object")
+    ap.add_argument("--full", action="store_true", help="besides the headline: its round-trip and zlib checks, the per-class rates, the "
+                                                        "roofline, the CPU baselines and (corpus config, one GPU) the side objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) as DIR/<name>.npy, "
+                                                                        "float32 / float64, at most 64 MB")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-inflate", action="store_true", help="--full: skip the inflate legs")
+    ap.add_argument("--no-api", action="store_true", help="--full: skip the host-buffer API leg")
+    ap.add_argument("--no-c2", action="store_true", help="--full, corpus config: skip the c2 side object")
+    ap.add_argument("--no-c5", action="store_true", help="--full, corpus config: skip the c5 side object")
     ap.add_argument("--no-corpus", action="store_true", help="(kept for old command lines: no effect)")
     args = ap.parse_args()
 
@@ -1206,7 +1297,8 @@ def main():
     eng = pkg.Engine(local_rank)
 
     if args.config == "c5":
-        line = c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, args.blocks or 163840, args.steps, args.warmup)
+        line = c5_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, args.blocks or 163840, args.steps, args.warmup,
+                          dump=args.dump_outputs)
         if line:
             print(json.dumps(line), flush=True)
     elif args.config == "c2":
@@ -1216,7 +1308,7 @@ def main():
             t = torch.tensor([n_c2], dtype=torch.int64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             n_c2 = int(t.item())
-        line = c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n_c2, args.steps, args.warmup)
+        line = c2_measure(torch, dist, args, rank, world, dev, distributed, pkg, eng, n_c2, args.steps, args.warmup, dump=args.dump_outputs)
         if line:
             print(json.dumps(line), flush=True)
     else:

@@ -2,7 +2,7 @@
 histories) through the HIP deflate engine, compared bit for bit with the oracle.  python tests/soak_gpu.py [seeds [blocks per seed]]"""
 import importlib, os, random, sys, zlib
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import oracle_lib as O

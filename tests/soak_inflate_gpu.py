@@ -4,7 +4,7 @@ engine (a stream per workgroup, a stream per lane with and without the fixed-cod
 python tests/soak_inflate_gpu.py [seeds]"""
 import importlib, os, random, sys, zlib
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import oracle_lib as O

@@ -4,7 +4,7 @@ the merged calls of nxz_engine.cpp (merged_deflate) with callers joining and lea
 too large to merge on their own pairs of lanes.  Every stream is read back by zlib and its checksums compared.
 python tests/soak_merged_gpu.py [seconds] [threads]"""
 import ctypes as C, importlib, os, random, sys, threading, time, zlib
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from datagen import make_block
 import zstream as Z

@@ -7,7 +7,7 @@ sizes (parts of the stream that begin and end anywhere: nxz_inflate_stream_part)
 whatever the engine declines.   python tests/soak_stream_gpu.py [cases]"""
 import importlib, os, random, sys, zlib
 import numpy as np
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 import corpus

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(script, *args, timeout=600):
-    env = dict(os.environ, GRAFT_REPO_ROOT=ROOT)
+    env = dict(os.environ)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", script)] + [str(a) for a in args], env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
     return p.stdout
