@@ -372,6 +372,69 @@ int nxz_batch_wrap(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n,
 int nxz_batch_pack_gzip(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
 			size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
 
+/* The zlib counterpart (RFC 1950): member i = CMF 0x78 and FLG with FLEVEL from `level` (0..9, -1 = 6, as
+ * zlib's deflateInit), job i's output -- or the same stored-block fallback as above --, the Adler-32 of
+ * results[i] big-endian.  offsets as above; `packed` needs n * 6 + sum(max(tpbc, length + 5)) bytes at most.
+ * Asynchronous on `stream`. */
+int nxz_batch_pack_zlib(nxz_ctx_t *ctx, int level, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
+			size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Framed streams on the device: zlib (RFC 1950) and gzip (RFC 1952)
+ * ---------------------------------------------------------------------- */
+enum { NXZ_FMT_ZLIB = 1, NXZ_FMT_GZIP = 2, NXZ_FMT_AUTO = 3 };   /* AUTO: per job, gzip when it starts 1f 8b, else zlib */
+enum {
+	NXZ_FRAME_OK = 0,
+	NXZ_FRAME_BAD_HEADER,    /* gzip ID1 ID2 / reserved FLG bits; zlib FCHECK / CINFO > 7; a job with resume or hist_len set */
+	NXZ_FRAME_BAD_METHOD,    /* CM != 8 */
+	NXZ_FRAME_NEED_DICT,     /* zlib FDICT: preset dictionaries are not supported, nothing is decoded (dictid is set) */
+	NXZ_FRAME_BAD_HCRC,      /* gzip FHCRC does not match the header */
+	NXZ_FRAME_TRUNCATED,     /* the source ends inside the header, the deflate data or the trailer */
+	NXZ_FRAME_DEFLATE,       /* the deflate data failed: results[i].cc says why */
+	NXZ_FRAME_BAD_CHECK,     /* Adler-32 / CRC-32 of the trailer differs from the output's */
+	NXZ_FRAME_BAD_LENGTH     /* gzip ISIZE differs from the output's length mod 2^32 */
+};
+/* One per job, written by the device (device memory, 52 bytes).  Offsets count from the job's src; 0 = absent. */
+typedef struct nxz_batch_frame {
+	uint32_t status;         /* NXZ_FRAME_* */
+	uint32_t format;         /* NXZ_FMT_ZLIB / NXZ_FMT_GZIP: what the job turned out to be */
+	uint32_t hdr_len;        /* header bytes */
+	uint32_t end;            /* bytes of src used: header + deflate + trailer (0 unless the trailer was read) */
+	uint32_t check;          /* the trailer as read: Adler-32 or CRC-32 */
+	uint32_t isize;          /* gzip ISIZE as read */
+	uint32_t mtime;          /* gzip MTIME */
+	uint32_t dictid;         /* zlib DICTID when FDICT is set */
+	uint32_t extra_off, extra_len, name_off, comment_off;
+	uint8_t  flg;            /* gzip FLG / zlib FLG */
+	uint8_t  xfl, os;        /* gzip XFL, OS */
+	uint8_t  cinfo;          /* zlib CINFO (CMF >> 4) */
+} nxz_batch_frame_t;
+
+/* Batched decompress of zlib / gzip streams: a header kernel parses every job's header and checks it, the
+ * deflate data goes through nxz_batch_decompress (the same routes as raw streams), a trailer kernel checks
+ * Adler-32 / CRC-32 and ISIZE.  jobs[], results[] and frames[] are DEVICE arrays; asynchronous on `stream`.
+ * jobs[].src may have any alignment; jobs[].dst must be 16-byte aligned (as for raw streams, or the streams
+ * take the slower route); resume and hist_len must be 0.  results[i] is what nxz_batch_decompress writes for
+ * the job's deflate data alone -- except after a header failure, when it is all zero with cc =
+ * NXZ_CC_INVALID_OP and dst is not touched.  Bytes after the trailer are no error: frames[i].end < src_len.
+ * A second member inside one job is not decoded. */
+int nxz_batch_decompress_framed(nxz_ctx_t *ctx, int fmt, const nxz_batch_job_t *jobs, size_t n,
+				nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
+
+/* A BGZF image (gzip members with the "BC" extra subfield, as nxz_batch_pack_gzip / nxz_blocked_deflate /
+ * bgzip write them) in DEVICE memory -> its plain bytes at dst (DEVICE).  The members are found on the device
+ * in parallel (every position that looks like a member header is a candidate; the members are the chain of
+ * candidates reachable from position 0), laid out by a prefix sum of their ISIZE -- offsets[j] (DEVICE,
+ * max_members + 1) -- and decoded as one framed gzip batch: frames[j] / results[j] (DEVICE, max_members)
+ * per member; a member that fails does not stop the others.  Members of 65 280 bytes of source keep every
+ * offset 16-byte aligned; other sizes decode correctly on the slower route.
+ * Synchronous.  Returns 0: *members, *out_len (sum of ISIZE), *consumed (the prefix of whole chained members,
+ * as nxz_blocked_scan).  -EILSEQ: packed does not start with a member; -E2BIG: more members than max_members
+ * (*members set) or dst_cap < sum of ISIZE (*out_len set). */
+int nxz_batch_unpack_gzip(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
+			  uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
+			  size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream);
+
 /* Device memory, pinned host memory, streams and asynchronous copies, for callers that hold
  * host buffers and do not link the HIP runtime themselves.  A stream made here is passed as
  * the `stream` argument of the batch calls; nxz_stream_destroy also releases the per-stream

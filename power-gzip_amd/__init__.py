@@ -8,4 +8,6 @@ from .engine import (Engine, EngineError, JOB_DTYPE, RESULT_DTYPE, DHT_DTYPE, li
                      FC_COMPRESS_FHT, FC_COMPRESS_FHT_COUNT, FC_COMPRESS_DHT, FC_COMPRESS_DHT_COUNT,
                      FC_COMPRESS_RESUME_FHT, FC_COMPRESS_RESUME_DHT_COUNT, FC_COMPRESS_DHTGEN,
                      FC_COMPRESS_DHTGEN_COUNT, FC_COMPRESS_RESUME_DHTGEN, FC_DECOMPRESS,
-                     FC_DECOMPRESS_RESUME, FC_WRAP)
+                     FC_DECOMPRESS_RESUME, FC_WRAP, FRAME_DTYPE, FMT_ZLIB, FMT_GZIP, FMT_AUTO, FRAME_OK,
+                     FRAME_BAD_HEADER, FRAME_BAD_METHOD, FRAME_NEED_DICT, FRAME_BAD_HCRC, FRAME_TRUNCATED, FRAME_DEFLATE,
+                     FRAME_BAD_CHECK, FRAME_BAD_LENGTH)

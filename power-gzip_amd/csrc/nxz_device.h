@@ -91,6 +91,14 @@ int nxz_launch_inflate_cut(const nxz_batch_job_t *jobs, size_t n, nxz_batch_resu
 			   unsigned pieces, uint8_t *workspace, size_t arena, hipStream_t stream);
 int nxz_launch_pack_members(const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n,
 			    uint64_t *offsets, uint8_t *packed, hipStream_t stream);
+int nxz_launch_pack_zlib(const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n, uint32_t flg,
+			 uint64_t *offsets, uint8_t *packed, hipStream_t stream);
+/* nxz_frame.hip: zlib / gzip framing around a raw inflate batch, and the members of a BGZF image */
+int nxz_launch_frame_header(int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames, nxz_batch_job_t *derived, hipStream_t stream);
+int nxz_launch_frame_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);
+size_t nxz_bgzf_workspace(uint64_t len, uint64_t cap);
+int nxz_launch_bgzf_discover(const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, uint64_t max_members, uint8_t *ws,
+			     uint64_t cap, nxz_batch_job_t **jobs, hipStream_t stream);   /* ws[0..3]: candidates, members, bytes covered, sum of ISIZE */
 int nxz_launch_inflate_lanes(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
 			     nxz_batch_dht_t *dht_io, uint8_t *workspace, int init_fixed, hipStream_t stream);
 /* nxz_inflate_wg.hip: a stream per workgroup, source, output and tables in LDS; what it cannot do goes a stream per wavefront behind it */

@@ -17,6 +17,7 @@
 #include <string.h>
 #include <time.h>
 #include <unistd.h>
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <map>
@@ -84,6 +85,11 @@ struct nxz_ctx {
 		size_t cut_cap = 0;
 		uint8_t *d_wg_ws = nullptr;               // a stream per workgroup (nxz_inflate_wg.hip): job counter, reasons, hand-back list
 		size_t wg_cap = 0;
+		nxz_batch_job_t *d_frame_jobs = nullptr;  // nxz_batch_decompress_framed: the derived raw jobs (the deflate bytes of each stream)
+		size_t frame_cap = 0;
+		uint8_t *d_bgzf_ws = nullptr;             // nxz_batch_unpack_gzip: the discovery's candidates, jump tables and the members' jobs
+		size_t bgzf_bytes = 0;
+		uint64_t bgzf_cap = 0;                    // ... candidates it has room for
 		// compress: what the LZ77 kernel hands to the entropy kernel, for one chunk of jobs
 		uint8_t *d_tokens = nullptr;              // chunk x NXZ_TOK_STRIDE
 		nxz_dht_prepared_t *d_gen = nullptr;      // tables the device generated, one per job of the chunk
@@ -116,6 +122,8 @@ struct nxz_ctx {
 			if (d_order_ws) (void)hipFree(d_order_ws);
 			if (d_cut_ws) (void)hipFree(d_cut_ws);
 			if (d_wg_ws) (void)hipFree(d_wg_ws);
+			if (d_frame_jobs) (void)hipFree(d_frame_jobs);
+			if (d_bgzf_ws) (void)hipFree(d_bgzf_ws);
 			if (d_tokens) (void)hipFree(d_tokens);                       // (d_gen and d_counts lie inside it)
 			if (d_cand2) (void)hipFree(d_cand2);
 			if (d_fuse) (void)hipFree(d_fuse);
@@ -124,6 +132,7 @@ struct nxz_ctx {
 	};
 	std::map<hipStream_t, Scratch> scratch;
 	std::map<hipStream_t, std::mutex> scratch_use;   // held by a batch call from sizing its stream's scratch to its last launch
+	std::map<hipStream_t, std::mutex> frame_use;     // held by a framed call from its header kernel to its trailer kernel (the derived jobs)
 	// nxz_deflate_host: a call works on two lanes, each with its own stream, so that the copies of one group of
 	// blocks run while the other group is in the kernels; HOST_PAIRS such pairs (made when first used, 100 MiB of device
 	// memory each), for callers on different threads (four pairs: 16 threads spent three quarters of a call waiting for one)
@@ -909,6 +918,125 @@ extern "C" int nxz_batch_pack_gzip(nxz_ctx_t *c, const nxz_batch_job_t *jobs, co
 	(void)hipSetDevice(c->device);
 	int rc = nxz_launch_pack_members(jobs, results, n, offsets, packed, (hipStream_t)stream);
 	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+extern "C" int nxz_batch_pack_zlib(nxz_ctx_t *c, int level, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n,
+				   uint64_t *offsets, uint8_t *packed, void *stream)
+{
+	if (!c || !jobs || !results || !offsets || !packed || n > 0xffffffffu || level < -1 || level > 9) return -EINVAL;
+	(void)hipSetDevice(c->device);
+	// FLEVEL as zlib's deflate.c writes it: 0 for levels 0-1, 1 for 2-5, 2 for 6 (and the default), 3 for 7-9
+	const uint32_t flevel = level < 0 || level == 6 ? 2 : level < 2 ? 0 : level < 6 ? 1 : 3;
+	uint32_t hdr = 0x78u << 8 | flevel << 6;
+	hdr += 31 - hdr % 31;
+	int rc = nxz_launch_pack_zlib(jobs, results, n, hdr & 0xff, offsets, packed, (hipStream_t)stream);
+	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
+// The caller holds c->frame_use[s].
+// ---------------------------------------------------------------------------
+static int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
+			 nxz_batch_frame_t *frames, hipStream_t s)
+{
+	nxz_batch_job_t *derived = nullptr;
+	{
+		std::lock_guard<std::mutex> g(c->mtx);
+		nxz_ctx::Scratch &sc = c->scratch[s];
+		if (sc.frame_cap < n) {
+			// grows only, as the workgroup kernel's workspace
+			if (sc.d_frame_jobs) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_frame_jobs); }
+			sc.d_frame_jobs = nullptr; sc.frame_cap = 0;
+			HIPCHK(hipMalloc((void **)&sc.d_frame_jobs, n * sizeof(nxz_batch_job_t)), return -ENOMEM);
+			sc.frame_cap = n;
+		}
+		derived = sc.d_frame_jobs;
+	}
+	int rc = nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
+	if (rc) { set_err("frame header launch", (hipError_t)rc); return -EIO; }
+	rc = batch_decompress(c, derived, n, results, nullptr, s, 0);
+	if (rc) return rc;
+	rc = nxz_launch_frame_trailer(jobs, n, results, frames, s);
+	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+static std::mutex *frame_mutex(nxz_ctx_t *c, hipStream_t s)
+{
+	std::lock_guard<std::mutex> g(c->mtx);
+	return &c->frame_use[s];
+}
+
+extern "C" int nxz_batch_decompress_framed(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n,
+					   nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	return framed_locked(c, fmt, jobs, n, results, frames, s);
+}
+
+// A BGZF image in device memory: the members found on the device (nxz_launch_bgzf_discover), then ONE wait for their count,
+// then the framed gzip path on them.
+extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
+				     uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
+				     size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream)
+{
+	if (members) *members = 0;
+	if (consumed) *consumed = 0;
+	if (out_len) *out_len = 0;
+	if (!c || (len && !packed) || !offsets || (max_members && (!frames || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (len < 26) return -EILSEQ;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	// room for the candidates: twice the members the caller allows, and one every 32 KiB (a true member has at most
+	// 64 KiB); an image with more -- false candidates in the payloads -- is run again with room for all of them
+	const uint64_t most = len / 4 + 1;                                   // (1f 8b 08 04 cannot overlap itself)
+	uint64_t cap = std::min<uint64_t>(most, std::max<uint64_t>((uint64_t)max_members * 2 + 1024, len / 32768 + 1024));
+	uint64_t ctl[4] = {0, 0, 0, 0};
+	nxz_batch_job_t *jobs = nullptr;
+	for (int pass = 0; pass < 2; pass++) {
+		uint8_t *ws = nullptr;
+		{
+			std::lock_guard<std::mutex> g(c->mtx);
+			nxz_ctx::Scratch &sc = c->scratch[s];
+			cap = std::max(cap, sc.bgzf_cap);
+			const size_t need = nxz_bgzf_workspace(len, cap);
+			if (sc.bgzf_bytes < need) {
+				if (sc.d_bgzf_ws) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_bgzf_ws); }
+				sc.d_bgzf_ws = nullptr; sc.bgzf_bytes = 0; sc.bgzf_cap = 0;
+				HIPCHK(hipMalloc((void **)&sc.d_bgzf_ws, need), return -ENOMEM);
+				sc.bgzf_bytes = need;
+			}
+			sc.bgzf_cap = std::max(sc.bgzf_cap, cap);
+			ws = sc.d_bgzf_ws;
+		}
+		int rc = nxz_launch_bgzf_discover(packed, len, dst, offsets, max_members, ws, cap, &jobs, s);
+		if (rc) { set_err("bgzf discovery launch", (hipError_t)rc); return -EIO; }
+		HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
+		HIPCHK(hipStreamSynchronize(s), return -EIO);
+		if (ctl[0] <= cap) break;
+		cap = ctl[0];                                                    // (every candidate, the second time)
+	}
+	const uint64_t L = ctl[1];
+	if (L == 0) return -EILSEQ;
+	if (members) *members = L;
+	if (consumed) *consumed = ctl[2];
+	if (L > max_members) return -E2BIG;
+	if (out_len) *out_len = ctl[3];
+	if (ctl[3] > dst_cap) return -E2BIG;
+	if (L >= (1u << 31)) return -E2BIG;
+	int rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)L, results, frames, s);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
 	return 0;
 }
 

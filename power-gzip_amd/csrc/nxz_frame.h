@@ -1,0 +1,162 @@
+// nxz_frame.h -- zlib (RFC 1950) and gzip (RFC 1952) headers, and the BGZF member check, as plain code that
+// compiles for the device (nxz_frame.hip: a wavefront per header) and for the host (tests/native/frame_host.cpp).
+//
+// The parser reads the header one field at a time and stops at the first fault, in zlib's order of checks
+// (inflate.c: FCHECK, method, window size, then FDICT; gzip: magic, method, reserved flags, the optional
+// fields, FHCRC).  A field that reaches past the source is NXZ_FRAME_TRUNCATED.  Two steps depend on who
+// runs it and are passed in as `Ops`:
+//   find_nul(p, from, len) -> index of the first 0 byte in [from, len), or len      (FNAME / FCOMMENT)
+//   crc32(p, n)            -> CRC-32 of n bytes                                    (FHCRC)
+// The device version looks at 64 bytes a step by ballot and computes the CRC in 64 slices combined by
+// multiplication with x^(8k) (nxz_crc_part below); the host version runs the same 64 slices one after the other.
+#ifndef NXZ_FRAME_H
+#define NXZ_FRAME_H
+#include <stdint.h>
+#include "../../include/nxz_engine.h"
+
+#if defined(__HIPCC__)
+#define NXZ_HD __host__ __device__
+#else
+#define NXZ_HD
+#endif
+
+NXZ_HD inline uint32_t nxz_rd16le(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+NXZ_HD inline uint32_t nxz_rd32le(const uint8_t *p) { return nxz_rd16le(p) | nxz_rd16le(p + 2) << 16; }
+NXZ_HD inline uint32_t nxz_rd32be(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+
+// ---- CRC-32 (reflected, polynomial 0xedb88320) in pieces --------------------------------------------------------
+// the register over n bytes from 0, without the initial and final inversion
+NXZ_HD inline uint32_t nxz_crc_raw(const uint8_t *p, uint32_t n)
+{
+	uint32_t c = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		c ^= p[i];
+		for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1) ? 0xedb88320u : 0);
+	}
+	return c;
+}
+// a * b mod P in the reflected representation (0x80000000 = 1)
+NXZ_HD inline uint32_t nxz_gf_mul(uint32_t a, uint32_t b)
+{
+	uint32_t r = 0;
+	for (int i = 0; i < 32; i++) {
+		r ^= (b & 0x80000000u) ? a : 0;
+		a = (a >> 1) ^ ((a & 1) ? 0xedb88320u : 0);
+		b <<= 1;
+	}
+	return r;
+}
+// x^(8 n) mod P
+NXZ_HD inline uint32_t nxz_x8n(uint32_t n)
+{
+	uint32_t r = 0x80000000u, sq = 0x00800000u;
+	while (n) { if (n & 1) r = nxz_gf_mul(r, sq); sq = nxz_gf_mul(sq, sq); n >>= 1; }
+	return r;
+}
+// slice k of NS over n bytes: [lo, hi)
+NXZ_HD inline void nxz_slice(uint32_t n, uint32_t ns, uint32_t k, uint32_t *lo, uint32_t *hi)
+{
+	const uint32_t per = (n + ns - 1) / ns;
+	const uint64_t a = (uint64_t)k * per, b = a + per;
+	*lo = a < n ? (uint32_t)a : n;
+	*hi = b < n ? (uint32_t)b : n;
+}
+// what slice [lo, hi) of n bytes adds to the register of all n (XOR the slices' parts, then nxz_crc_finish)
+NXZ_HD inline uint32_t nxz_crc_part(const uint8_t *p, uint32_t lo, uint32_t hi, uint32_t n)
+{
+	return lo < hi ? nxz_gf_mul(nxz_crc_raw(p + lo, hi - lo), nxz_x8n(n - hi)) : 0;
+}
+NXZ_HD inline uint32_t nxz_crc_finish(uint32_t parts, uint32_t n) { return ~(parts ^ nxz_gf_mul(0xffffffffu, nxz_x8n(n))); }
+
+// ---- the header --------------------------------------------------------------------------------------------------
+// Fills f (status, format, hdr_len and the header's fields; end / check / isize are the trailer's, left 0) and
+// returns the status.  fmt: NXZ_FMT_ZLIB / _GZIP / _AUTO.
+template <class Ops>
+NXZ_HD inline uint32_t nxz_frame_parse(const uint8_t *p, uint32_t len, int fmt, nxz_batch_frame_t *f, Ops &ops)
+{
+	*f = nxz_batch_frame_t();
+	const bool gz = fmt == NXZ_FMT_GZIP || (fmt == NXZ_FMT_AUTO && len >= 2 && p[0] == 0x1f && p[1] == 0x8b);
+	f->format = gz ? NXZ_FMT_GZIP : NXZ_FMT_ZLIB;
+	uint32_t st = NXZ_FRAME_OK;
+	if (!gz) {
+		if (len < 2) st = NXZ_FRAME_TRUNCATED;
+		else {
+			const uint32_t cmf = p[0], flg = p[1];
+			f->flg = (uint8_t)flg; f->cinfo = (uint8_t)(cmf >> 4);
+			if ((cmf * 256 + flg) % 31) st = NXZ_FRAME_BAD_HEADER;
+			else if ((cmf & 15) != 8) st = NXZ_FRAME_BAD_METHOD;
+			else if ((cmf >> 4) > 7) st = NXZ_FRAME_BAD_HEADER;
+			else if (flg & 0x20) {
+				if (len < 6) st = NXZ_FRAME_TRUNCATED;
+				else { f->dictid = nxz_rd32be(p + 2); f->hdr_len = 6; st = NXZ_FRAME_NEED_DICT; }
+			} else f->hdr_len = 2;
+		}
+		f->status = st;
+		return st;
+	}
+	uint32_t q = 10;
+	if (len < 1) st = NXZ_FRAME_TRUNCATED;
+	else if (p[0] != 0x1f) st = NXZ_FRAME_BAD_HEADER;
+	else if (len < 2) st = NXZ_FRAME_TRUNCATED;
+	else if (p[1] != 0x8b) st = NXZ_FRAME_BAD_HEADER;
+	else if (len < 3) st = NXZ_FRAME_TRUNCATED;
+	else if (p[2] != 8) st = NXZ_FRAME_BAD_METHOD;
+	else if (len < 4) st = NXZ_FRAME_TRUNCATED;
+	else if ((f->flg = p[3]) & 0xe0) st = NXZ_FRAME_BAD_HEADER;
+	else if (len < 10) st = NXZ_FRAME_TRUNCATED;
+	else {
+		const uint32_t flg = p[3];
+		f->mtime = nxz_rd32le(p + 4); f->xfl = p[8]; f->os = p[9];
+		if (flg & 4) {
+			if (len < q + 2) st = NXZ_FRAME_TRUNCATED;
+			else {
+				f->extra_len = nxz_rd16le(p + q);
+				f->extra_off = q + 2;
+				q += 2 + f->extra_len;
+				if (q > len) st = NXZ_FRAME_TRUNCATED;
+			}
+		}
+		if (st == NXZ_FRAME_OK && (flg & 8)) {
+			f->name_off = q;
+			const uint32_t z = q < len ? ops.find_nul(p, q, len) : len;
+			if (z >= len) st = NXZ_FRAME_TRUNCATED; else q = z + 1;
+		}
+		if (st == NXZ_FRAME_OK && (flg & 16)) {
+			f->comment_off = q;
+			const uint32_t z = q < len ? ops.find_nul(p, q, len) : len;
+			if (z >= len) st = NXZ_FRAME_TRUNCATED; else q = z + 1;
+		}
+		if (st == NXZ_FRAME_OK && (flg & 2)) {
+			if (len < q + 2) st = NXZ_FRAME_TRUNCATED;
+			else {
+				if ((ops.crc32(p, q) & 0xffff) != nxz_rd16le(p + q)) st = NXZ_FRAME_BAD_HCRC;
+				q += 2;
+			}
+		}
+		if (st == NXZ_FRAME_OK) f->hdr_len = q;
+	}
+	f->status = st;
+	return st;
+}
+
+// ---- BGZF: one member with the "BC" subfield at p (left bytes from there on) -------------------------------------
+// Its total size (BSIZE + 1), or 0.  The checks of the host's scanner (nxz_blocked.cpp member_size): FLG = FEXTRA
+// alone, XLEN >= 6, the subfield anywhere among the others, the size covers header and trailer and lies inside `left`.
+NXZ_HD inline uint32_t nxz_bgzf_member_size(const uint8_t *p, uint64_t left)
+{
+	if (left < 12 + 6 + 8 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return 0;
+	const uint32_t xlen = nxz_rd16le(p + 10);
+	if (xlen < 6 || 12 + (uint64_t)xlen + 8 > left) return 0;
+	for (uint32_t q = 0; q + 4 <= xlen;) {
+		const uint8_t *s = p + 12 + q;
+		const uint32_t slen = nxz_rd16le(s + 2);
+		if (s[0] == 'B' && s[1] == 'C' && slen == 2 && q + 6 <= xlen) {
+			const uint32_t size = nxz_rd16le(s + 4) + 1;
+			return size >= 12 + xlen + 8 && size <= left ? size : 0;
+		}
+		q += 4 + slen;
+	}
+	return 0;
+}
+
+#endif

@@ -325,6 +325,86 @@ __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t
 	}
 }
 
+// ---- zlib streams from a compress batch (RFC 1950) ----------------------------------------------
+// The same members in zlib framing: CMF FLG, the payload (the job's output or its stored block, member_stored), Adler-32
+// big-endian.  Offsets as member_offsets_kernel, with the zlib overhead.
+#define NXZ_ZLIB_OVERHEAD 6u         /* CMF FLG + Adler-32 */
+
+__device__ inline uint32_t zlib_member_size(const nxz_batch_job_t &job, const nxz_batch_result_t &r)
+{
+	return NXZ_ZLIB_OVERHEAD + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
+}
+
+__global__ __launch_bounds__(1024) void zlib_offsets_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+							    uint32_t n, uint64_t *__restrict__ offsets)
+{
+	__shared__ uint64_t part[1024];
+	const uint32_t t = threadIdx.x;
+	const uint32_t per = (n + 1023) / 1024;
+	const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+	uint64_t sum = 0;
+	for (uint32_t i = lo; i < hi; i++) sum += zlib_member_size(jobs[i], results[i]);
+	part[t] = sum;
+	__syncthreads();
+	for (uint32_t d = 1; d < 1024; d <<= 1) {
+		uint64_t v = t >= d ? part[t - d] : 0;
+		__syncthreads();
+		part[t] += v;
+		__syncthreads();
+	}
+	uint64_t off = part[t] - sum;
+	for (uint32_t i = lo; i < hi; i++) {
+		offsets[i] = off;
+		off += zlib_member_size(jobs[i], results[i]);
+	}
+	if (t == 1023) offsets[n] = part[1023];
+}
+
+// one workgroup per stream, written as pack_members_kernel writes a gzip member
+__global__ __launch_bounds__(256) void pack_zlib_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+							const uint64_t *__restrict__ offsets, uint32_t flg, uint8_t *__restrict__ packed)
+{
+	const uint32_t t = threadIdx.x;
+	const nxz_batch_job_t job = jobs[blockIdx.x];
+	const nxz_batch_result_t r = results[blockIdx.x];
+	const uint64_t off = offsets[blockIdx.x];
+	const uint32_t len = job.src_len - job.hist_len;
+	const bool stored = member_stored(job, r);
+	const uint32_t size = zlib_member_size(job, r);
+	const uint32_t d0 = stored ? 7 : 2;                           // first byte that comes from `data`
+	const uint32_t dn = stored ? len : r.tpbc;
+	const uint8_t *data = stored ? job.src + job.hist_len : job.dst;
+	auto byte_at = [&](uint32_t j) -> uint32_t {
+		if (j < 2) return j == 0 ? 0x78u : flg;                 // CM 8, CINFO 7 (a 32 KiB window)
+		if (j < d0) {                                           // stored block: BFINAL=1 BTYPE=00, LEN, NLEN
+			const uint32_t k = j - 2;
+			return k == 0 ? 1 : k < 3 ? (len >> (8 * (k - 1))) & 0xff : (~len >> (8 * (k - 3))) & 0xff;
+		}
+		if (j < d0 + dn) return data[j - d0];
+		return (r.adler >> (8 * (3 - (j - d0 - dn)))) & 0xff;   // Adler-32, most significant byte first
+	};
+	uint8_t *o = packed + off;
+	const uint32_t head = (uint32_t)((4 - ((uintptr_t)o & 3)) & 3);
+	const uint32_t nd = size > head ? (size - head) >> 2 : 0;
+	if (t < head && t < size) o[t] = (uint8_t)byte_at(t);
+	for (uint32_t k = head + nd * 4 + t; k < size; k += 256) o[k] = (uint8_t)byte_at(k);
+	uint32_t *od = (uint32_t *)(o + head);
+	for (uint32_t w = t; w < nd; w += 256) {
+		const uint32_t j = head + w * 4;
+		uint32_t v;
+		if (j >= d0 && j + 4 <= d0 + dn) {
+			const uintptr_t a = (uintptr_t)data + (j - d0);
+			const uint32_t *q = (const uint32_t *)(a & ~(uintptr_t)3);
+			const uint32_t bo = (uint32_t)a & 3;
+			const uint32_t lo = q[0], hi = bo ? q[1] : 0;
+			v = __builtin_amdgcn_alignbyte(hi, lo, bo);
+		} else {
+			v = byte_at(j) | byte_at(j + 1) << 8 | byte_at(j + 2) << 16 | byte_at(j + 3) << 24;
+		}
+		od[w] = v;
+	}
+}
+
 // ---- one deflate stream from a compress batch ---------------------------------------------------
 // The blocks of a batch, made independently, laid back to back as ONE raw deflate stream the way
 // the reference strings its jobs together: a block that ends inside a byte is followed by an
@@ -540,6 +620,15 @@ extern "C" int nxz_launch_pack_members(const nxz_batch_job_t *jobs, const nxz_ba
 	if (!n) return 0;
 	hipLaunchKernelGGL(nxz::member_offsets_kernel, dim3(1), dim3(1024), 0, stream, jobs, results, (uint32_t)n, offsets);
 	hipLaunchKernelGGL(nxz::pack_members_kernel, dim3((unsigned)n), dim3(256), 0, stream, jobs, results, offsets, packed);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_pack_zlib(const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n, uint32_t flg,
+				    uint64_t *offsets, uint8_t *packed, hipStream_t stream)
+{
+	if (!n) return 0;
+	hipLaunchKernelGGL(nxz::zlib_offsets_kernel, dim3(1), dim3(1024), 0, stream, jobs, results, (uint32_t)n, offsets);
+	hipLaunchKernelGGL(nxz::pack_zlib_kernel, dim3((unsigned)n), dim3(256), 0, stream, jobs, results, offsets, flg, packed);
 	return (int)hipGetLastError();
 }
 

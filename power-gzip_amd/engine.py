@@ -32,6 +32,15 @@ RESULT_DTYPE = np.dtype([("cc", "<u4"), ("tpbc", "<u4"), ("tebc", "<u4"), ("spbc
 DHT_DTYPE = np.dtype([("dhtlen", "<u4"), ("dht", "u1", (292,))])
 assert JOB_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 32 and DHT_DTYPE.itemsize == 296
 
+# framed streams (include/nxz_engine.h: nxz_batch_decompress_framed / nxz_batch_unpack_gzip)
+FMT_ZLIB, FMT_GZIP, FMT_AUTO = 1, 2, 3
+(FRAME_OK, FRAME_BAD_HEADER, FRAME_BAD_METHOD, FRAME_NEED_DICT, FRAME_BAD_HCRC, FRAME_TRUNCATED, FRAME_DEFLATE,
+ FRAME_BAD_CHECK, FRAME_BAD_LENGTH) = range(9)
+FRAME_DTYPE = np.dtype([("status", "<u4"), ("format", "<u4"), ("hdr_len", "<u4"), ("end", "<u4"), ("check", "<u4"),
+                        ("isize", "<u4"), ("mtime", "<u4"), ("dictid", "<u4"), ("extra_off", "<u4"), ("extra_len", "<u4"),
+                        ("name_off", "<u4"), ("comment_off", "<u4"), ("flg", "u1"), ("xfl", "u1"), ("os", "u1"), ("cinfo", "u1")])
+assert FRAME_DTYPE.itemsize == 52
+
 
 class StreamResume(C.Structure):
     """nxz_stream_resume_t (include/nxz_engine.h): where a deflate stream stands between two calls"""
@@ -73,6 +82,11 @@ def load_library():
         L.nxz_batch_dhtgen.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.nxz_batch_decompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_wrap.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_batch_pack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_pack_zlib.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_decompress_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_inflate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -179,6 +193,58 @@ class Engine:
                                          dht_io.data_ptr() if dht_io is not None else None, self.stream_handle())
         self._check(rc, "nxz_batch_decompress")
         return results
+
+    def decompress_framed(self, fmt, jobs, n, results=None, frames=None):
+        """zlib / gzip streams (FMT_ZLIB / FMT_GZIP / FMT_AUTO), nxz_batch_decompress_framed.  Returns (results, frames),
+        device tensors of n RESULT_DTYPE / FRAME_DTYPE records."""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if frames is None:
+            frames = t.empty(n * FRAME_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_decompress_framed(self.ctx, fmt, jobs.data_ptr(), n, results.data_ptr(), frames.data_ptr(),
+                                                self.stream_handle())
+        self._check(rc, "nxz_batch_decompress_framed")
+        return results, frames
+
+    def frames_to_host(self, frames):
+        self.torch.cuda.synchronize(self.dev)
+        return frames.cpu().numpy().view(FRAME_DTYPE)
+
+    def unpack_gzip(self, packed, length, dst, max_members, offsets=None, frames=None, results=None):
+        """a BGZF image (uint8 device tensor, `length` bytes from its start) -> dst (uint8 device tensor), nxz_batch_unpack_gzip.
+        Returns (rc, dict): rc 0 / -errno; dict holds members, consumed, out_len and the device tensors offsets, frames, results."""
+        t = self.torch
+        if offsets is None:
+            offsets = t.empty(max_members + 1, dtype=t.int64, device=self.dev)
+        if frames is None:
+            frames = t.empty(max(1, max_members) * FRAME_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if results is None:
+            results = t.empty(max(1, max_members) * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        members, consumed, out_len = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self.L.nxz_batch_unpack_gzip(self.ctx, packed.data_ptr(), length, dst.data_ptr(), dst.numel(), offsets.data_ptr(),
+                                          frames.data_ptr(), results.data_ptr(), max_members, C.byref(members), C.byref(consumed),
+                                          C.byref(out_len), self.stream_handle())
+        return rc, {"members": members.value, "consumed": consumed.value, "out_len": out_len.value,
+                    "offsets": offsets, "frames": frames, "results": results}
+
+    def pack_gzip(self, jobs, results, n, packed, offsets=None):
+        """BGZF members from a compress batch, nxz_batch_pack_gzip.  Returns the offsets (int64 device tensor, n + 1)."""
+        t = self.torch
+        if offsets is None:
+            offsets = t.empty(n + 1, dtype=t.int64, device=self.dev)
+        self._check(self.L.nxz_batch_pack_gzip(self.ctx, jobs.data_ptr(), results.data_ptr(), n, offsets.data_ptr(), packed.data_ptr(),
+                                               self.stream_handle()), "nxz_batch_pack_gzip")
+        return offsets
+
+    def pack_zlib(self, level, jobs, results, n, packed, offsets=None):
+        """zlib streams from a compress batch, nxz_batch_pack_zlib.  Returns the offsets (int64 device tensor, n + 1)."""
+        t = self.torch
+        if offsets is None:
+            offsets = t.empty(n + 1, dtype=t.int64, device=self.dev)
+        self._check(self.L.nxz_batch_pack_zlib(self.ctx, level, jobs.data_ptr(), results.data_ptr(), n, offsets.data_ptr(),
+                                               packed.data_ptr(), self.stream_handle()), "nxz_batch_pack_zlib")
+        return offsets
 
     def copy_device(self, dst, src):
         """dst <- src (uint8 device tensors of equal size, a multiple of 16 bytes) by the engine's 16-bytes-a-lane copy kernel"""
