@@ -52,6 +52,31 @@ int nxz_blocked_scan(const void *src, size_t len, uint64_t *members, uint64_t *u
 int nxz_blocked_inflate(const void *src, size_t len, const nxz_blocked_opts_t *opts,
 			nxz_sink_fn sink, void *user, uint64_t *out_len, size_t *consumed);
 
+/* BGZF indexes (.gzi, as bgzip -i / -r writes them): a little-endian uint64 count k, then k pairs of
+ * little-endian uint64 (compressed offset, uncompressed offset), the starts of the members after the
+ * first (its (0, 0) is implicit), in increasing order.  A member index as nxz_bgzf_index gives it
+ * (coff / uoff, HOST, nidx = members + 1 entries) -> the starts of members 1 .. members - 1 to `sink`. */
+int nxz_gzi_write(const uint64_t *coff, const uint64_t *uoff, uint64_t nidx, nxz_sink_fn sink, void *user);
+
+/* A .gzi file's bytes -> coff[0..k] / uoff[0..k] (HOST, max_entries; (0, 0) first, then the file's
+ * entries), *entries = k + 1.  Either array may be NULL to ask for *entries alone.  The last entry may
+ * point at the end marker or at the end of the data.  Returns 0; -EILSEQ: truncated, trailing bytes, or
+ * offsets not increasing (uncompressed ones may repeat, compressed ones may not); -E2BIG: more entries
+ * than max_entries (*entries set). */
+int nxz_gzi_read(const void *buf, size_t len, uint64_t *coff, uint64_t *uoff, size_t max_entries, uint64_t *entries);
+
+/* Uncompressed bytes [offset, offset + size) of a BGZF image held in HOST memory, to `sink`.  src holds
+ * the image from compressed offset src_off on (src_len bytes).  coff / uoff (HOST, nstarts) are member
+ * starts as nxz_gzi_read gives them, absolute, or NULL / 0: the members are found by walking src (src_off
+ * must then be 0).  The starts may stop short of the end of src: the members behind the last one are
+ * walked on the host.  Only the compressed span of the members the range needs goes to the device
+ * (nxz_bgzf_read_ranges).  A range that reaches past the end of the data is cut there.  Returns 0;
+ * -ERANGE: offset lies outside the data (nothing written);
+ * -EILSEQ: the starts do not match the data, or a member is damaged; or a negative errno. */
+int nxz_gzi_read_range(const void *src, uint64_t src_off, size_t src_len, const uint64_t *coff, const uint64_t *uoff,
+		       uint64_t nstarts, uint64_t offset, uint64_t size, const nxz_blocked_opts_t *opts,
+		       nxz_sink_fn sink, void *user);
+
 #ifdef __cplusplus
 }
 #endif

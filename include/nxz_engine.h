@@ -435,6 +435,49 @@ int nxz_batch_unpack_gzip(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t len, u
 			  uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
 			  size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream);
 
+/* ------------------------------------------------------------------------
+ * BGZF random access: the member index and batched range reads
+ * ---------------------------------------------------------------------- */
+/* The member index of a BGZF image in DEVICE memory (found as nxz_batch_unpack_gzip finds the members):
+ * coff[j] / uoff[j] (DEVICE, max_members + 1) = compressed / uncompressed offset of member j; coff[L] = the
+ * bytes of whole chained members (nxz_blocked_scan's `consumed`), uoff[L] = sum of ISIZE.  Empty members
+ * (the end marker) are members: uoff may repeat.  Synchronous (one wait, for L).  Returns 0 and *members = L;
+ * -EILSEQ: packed does not start with a member; -E2BIG: L > max_members (*members set, nothing written). */
+int nxz_bgzf_index(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t len, uint64_t *coff, uint64_t *uoff,
+		   size_t max_members, uint64_t *members, void *stream);
+
+typedef struct nxz_bgzf_range { uint64_t begin, end; } nxz_bgzf_range_t;      /* [begin, end) */
+enum { NXZ_RANGE_UOFF = 0, NXZ_RANGE_VOFF = 1 };      /* ranges in uncompressed offsets / virtual offsets (coff << 16 | within) */
+enum {
+	NXZ_RANGE_OK = 0,
+	NXZ_RANGE_OUT_OF_BOUNDS, /* begin > end, begin < uoff[0] or end > uoff[L] (after conversion): no bytes */
+	NXZ_RANGE_BAD_VOFFSET,   /* voff >> 16 is no coff[j], or voff & 0xffff exceeds that member's ISIZE: no bytes */
+	NXZ_RANGE_DAMAGED        /* a member it touches failed its framed decode, or its ISIZE is not uoff[j+1] - uoff[j]: zeros */
+};
+
+/* Reads n ranges of a BGZF image.  coff / uoff (DEVICE, nidx = members + 1 entries) is an index as nxz_bgzf_index
+ * writes it, or a SLICE of one (entries i..i+k): packed then holds the image's bytes from coff[0] on (packed_len of
+ * them), and ranges are in the index's absolute offsets.  ranges (DEVICE, n).
+ *   uncompressed byte u lies in the last member j with uoff[j] <= u (upper_bound - 1; empty members hold nothing);
+ *   a virtual offset needs voff >> 16 == coff[j] for some j <= L and voff & 0xffff <= ISIZE of j (== ISIZE: the
+ *   member's end, as htslib allows); it stands for uoff[j] + (voff & 0xffff);
+ *   an empty range is NXZ_RANGE_OK with no bytes; begin > end, begin < uoff[0], end > uoff[L] are OUT_OF_BOUNDS.
+ * Range r's bytes go to dst + offsets[r] (offsets DEVICE, n + 1, written by the engine: the exclusive prefix sum of
+ * the ranges' lengths, 0 for a range that is not OK); status[r] (DEVICE, NXZ_RANGE_*).  A DAMAGED range's bytes are
+ * zero; the other ranges are unaffected.  Every member is decoded at most once per call, however many ranges touch
+ * it (into a 16-byte aligned slot of per-stream scratch, in chunks of at most NXZ_BGZF_CHUNK members -- default
+ * 16 384 -- and 1 GiB), then the pieces are copied to dst.
+ * Before anything is decoded the device checks that the index describes the image: nxz_bgzf_member_size at every
+ * coff[j] - coff[0] must be coff[j+1] - coff[j], and uoff must not decrease.  Synchronous.
+ * Returns 0; -EILSEQ: the index does not describe the image (nothing written); -E2BIG: dst_cap is too small
+ * (*out_len = the bytes needed; offsets and status written, dst not); -EINVAL.  *out_len = bytes of all ranges,
+ * *decoded = members inflated (either may be NULL). */
+int nxz_bgzf_read_ranges(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t packed_len,
+			 const uint64_t *coff, const uint64_t *uoff, uint64_t nidx,
+			 int kind, const nxz_bgzf_range_t *ranges, size_t n,
+			 uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,
+			 uint64_t *out_len, uint64_t *decoded, void *stream);
+
 /* Device memory, pinned host memory, streams and asynchronous copies, for callers that hold
  * host buffers and do not link the HIP runtime themselves.  A stream made here is passed as
  * the `stream` argument of the batch calls; nxz_stream_destroy also releases the per-stream

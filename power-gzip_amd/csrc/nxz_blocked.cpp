@@ -371,3 +371,104 @@ extern "C" int nxz_blocked_inflate(const void *src_, size_t len, const nxz_block
 		mem.size(), t_setup.t, t_stage.t, t_wait.t, t_sink.t);
 	return rc;
 }
+
+// ---------------------------------------------------------------------------
+// BGZF indexes (.gzi) and ranges of a host image through the device's range reader
+// ---------------------------------------------------------------------------
+namespace {
+inline void wr64(uint8_t *p, uint64_t v) { for (int i = 0; i < 8; i++) p[i] = (uint8_t)(v >> (8 * i)); }
+inline uint64_t rd64(const uint8_t *p) { uint64_t v = 0; for (int i = 7; i >= 0; i--) v = v << 8 | p[i]; return v; }
+}
+
+extern "C" int nxz_gzi_write(const uint64_t *coff, const uint64_t *uoff, uint64_t nidx, nxz_sink_fn sink, void *user)
+{
+	if (!sink || (nidx && (!coff || !uoff))) return -EINVAL;
+	const uint64_t k = nidx >= 2 ? nidx - 2 : 0;                       // members 1 .. L - 1
+	std::vector<uint8_t> b(8 + 16 * k);
+	wr64(b.data(), k);
+	for (uint64_t j = 0; j < k; j++) { wr64(&b[8 + 16 * j], coff[j + 1]); wr64(&b[16 + 16 * j], uoff[j + 1]); }
+	return sink(user, b.data(), b.size()) ? -EIO : 0;
+}
+
+extern "C" int nxz_gzi_read(const void *buf_, size_t len, uint64_t *coff, uint64_t *uoff, size_t max_entries, uint64_t *entries)
+{
+	if (entries) *entries = 0;
+	const uint8_t *buf = (const uint8_t *)buf_;
+	if (len && !buf) return -EINVAL;
+	if (len < 8) return -EILSEQ;
+	const uint64_t k = rd64(buf);
+	if (k > (len - 8) / 16 || len != 8 + 16 * k) return -EILSEQ;
+	uint64_t pc = 0, pu = 0;
+	for (uint64_t j = 0; j < k; j++) {
+		const uint64_t c = rd64(buf + 8 + 16 * j), u = rd64(buf + 16 + 16 * j);
+		if (c <= pc || u < pu) return -EILSEQ;
+		pc = c; pu = u;
+	}
+	if (entries) *entries = k + 1;
+	if (!coff || !uoff) return 0;
+	if (k + 1 > max_entries) return -E2BIG;
+	coff[0] = uoff[0] = 0;
+	for (uint64_t j = 0; j < k; j++) { coff[j + 1] = rd64(buf + 8 + 16 * j); uoff[j + 1] = rd64(buf + 16 + 16 * j); }
+	return 0;
+}
+
+extern "C" int nxz_gzi_read_range(const void *src_, uint64_t src_off, size_t src_len, const uint64_t *coff, const uint64_t *uoff,
+				  uint64_t nstarts, uint64_t offset, uint64_t size, const nxz_blocked_opts_t *opts, nxz_sink_fn sink, void *user)
+{
+	const uint8_t *src = (const uint8_t *)src_;
+	if (!sink || (src_len && !src) || (nstarts && (!coff || !uoff)) || (!nstarts && src_off)) return -EINVAL;
+	// the complete index of what src holds: the given starts inside it, then the members walked behind the last one
+	std::vector<uint64_t> C, U;
+	for (uint64_t j = 0; j < nstarts; j++) {
+		if (coff[j] < src_off) continue;
+		if (coff[j] >= src_off + src_len) break;
+		C.push_back(coff[j]); U.push_back(uoff[j]);
+	}
+	if (C.empty()) {
+		if (nstarts) return -ERANGE;
+		C.push_back(0); U.push_back(0);
+	}
+	if (C[0] != src_off) return -EILSEQ;
+	for (uint64_t at = C.back() - src_off, walked = 0;; walked++) {
+		const size_t sz = at < src_len ? member_size(src + at, src_len - at) : 0;
+		if (!sz) { if (!walked) return -EILSEQ; break; }
+		U.push_back(U.back() + rd32(src + at + sz - 4));
+		at += sz;
+		C.push_back(src_off + at);
+	}
+	const uint64_t L = C.size() - 1;
+	if (offset < U[0] || offset > U[L]) return -ERANGE;
+	size = std::min(size, U[L] - offset);
+	if (!size) return 0;
+	// the members the range needs: [j0, j1]
+	const uint64_t j0 = (uint64_t)(std::upper_bound(U.begin(), U.begin() + L, offset) - U.begin()) - 1;
+	const uint64_t j1 = (uint64_t)(std::upper_bound(U.begin(), U.begin() + L, offset + size - 1) - U.begin()) - 1;
+	const uint64_t span = C[j1 + 1] - C[j0], nidx = j1 - j0 + 2;
+	Ctx ctx(opts ? opts->device : -1);
+	if (!ctx.c) return -ENODEV;
+	Set S;
+	S.c = ctx.c;
+	S.stream = nxz_stream_create(ctx.c);
+	uint8_t *d_src = S.dmalloc<uint8_t>(span + 16), *d_dst = S.dmalloc<uint8_t>(size + 16);
+	uint64_t *d_idx = S.dmalloc<uint64_t>(2 * nidx + 2 + 1);
+	nxz_bgzf_range_t *d_rng = S.dmalloc<nxz_bgzf_range_t>(1);
+	uint32_t *d_st = S.dmalloc<uint32_t>(1);
+	uint8_t *h_dst = S.pmalloc<uint8_t>(size);
+	if (!S.stream || !d_src || !d_dst || !d_idx || !d_rng || !d_st || !h_dst) return -ENOMEM;
+	uint64_t *d_coff = d_idx, *d_uoff = d_idx + nidx, *d_off = d_idx + 2 * nidx;
+	const nxz_bgzf_range_t r = {offset, offset + size};
+	int rc = nxz_copy_to_device(ctx.c, d_src, src + (C[j0] - src_off), span, S.stream);
+	if (!rc) rc = nxz_copy_to_device(ctx.c, d_coff, &C[j0], nidx * 8, S.stream);
+	if (!rc) rc = nxz_copy_to_device(ctx.c, d_uoff, &U[j0], nidx * 8, S.stream);
+	if (!rc) rc = nxz_copy_to_device(ctx.c, d_rng, &r, sizeof(r), S.stream);
+	uint64_t out = 0;
+	if (!rc) rc = nxz_bgzf_read_ranges(ctx.c, d_src, span, d_coff, d_uoff, nidx, NXZ_RANGE_UOFF, d_rng, 1, d_dst, size, d_off, d_st,
+					   &out, nullptr, S.stream);
+	uint32_t st = 0;
+	if (!rc) rc = nxz_copy_to_host(ctx.c, &st, d_st, 4, S.stream);
+	if (!rc) rc = nxz_copy_to_host(ctx.c, h_dst, d_dst, size, S.stream);
+	if (!rc) rc = nxz_ctx_sync(ctx.c, S.stream);
+	if (rc) return rc;
+	if (st != NXZ_RANGE_OK || out != size) return -EILSEQ;
+	return sink(user, h_dst, size) ? -EIO : 0;
+}

@@ -99,6 +99,17 @@ int nxz_launch_frame_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_re
 size_t nxz_bgzf_workspace(uint64_t len, uint64_t cap);
 int nxz_launch_bgzf_discover(const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, uint64_t max_members, uint8_t *ws,
 			     uint64_t cap, nxz_batch_job_t **jobs, hipStream_t stream);   /* ws[0..3]: candidates, members, bytes covered, sum of ISIZE */
+int nxz_launch_bgzf_coff(const uint8_t *packed, uint64_t len, uint8_t *ws, uint64_t cap, uint64_t max_members, uint64_t *coff, hipStream_t stream);
+/* nxz_bgzf.hip: ranges of a BGZF image through its member index (ws[0..4]: index faulty, needed members, bytes, pieces, largest member) */
+size_t nxz_bgzf_ranges_workspace(uint64_t n, uint64_t L);
+int nxz_launch_bgzf_map(const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff, uint64_t L, int kind,
+			const nxz_bgzf_range_t *ranges, uint64_t n, uint64_t *offsets, uint32_t *status, uint8_t *ws, hipStream_t stream);
+int nxz_launch_bgzf_jobs(const uint8_t *packed, const uint64_t *coff, const uint64_t *uoff, uint64_t n, uint64_t L, uint8_t *ws,
+			 uint64_t k0, uint64_t cnt, uint8_t *slots, uint64_t stride, nxz_batch_job_t *jobs, hipStream_t stream);
+int nxz_launch_bgzf_gather(const uint64_t *uoff, uint64_t n, uint64_t L, uint64_t pieces, uint8_t *ws, const uint64_t *offsets,
+			   const uint8_t *slots, uint64_t stride, uint64_t k0, uint64_t cnt, const nxz_batch_frame_t *frames,
+			   const nxz_batch_result_t *results, uint8_t *dst, uint32_t *status, hipStream_t stream);
+int nxz_launch_bgzf_zero(uint64_t n, const uint64_t *offsets, const uint32_t *status, uint8_t *dst, hipStream_t stream);
 int nxz_launch_inflate_lanes(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
 			     nxz_batch_dht_t *dht_io, uint8_t *workspace, int init_fixed, hipStream_t stream);
 /* nxz_inflate_wg.hip: a stream per workgroup, source, output and tables in LDS; what it cannot do goes a stream per wavefront behind it */

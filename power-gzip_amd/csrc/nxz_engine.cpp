@@ -90,6 +90,10 @@ struct nxz_ctx {
 		uint8_t *d_bgzf_ws = nullptr;             // nxz_batch_unpack_gzip: the discovery's candidates, jump tables and the members' jobs
 		size_t bgzf_bytes = 0;
 		uint64_t bgzf_cap = 0;                    // ... candidates it has room for
+		uint8_t *d_rng_ws = nullptr;              // nxz_bgzf_read_ranges: the map's per-range and per-member arrays
+		size_t rng_bytes = 0;
+		uint8_t *d_rng_slots = nullptr;           // ... a chunk of decoded members (16-byte aligned slots), their jobs, frames and results
+		size_t slots_bytes = 0;
 		// compress: what the LZ77 kernel hands to the entropy kernel, for one chunk of jobs
 		uint8_t *d_tokens = nullptr;              // chunk x NXZ_TOK_STRIDE
 		nxz_dht_prepared_t *d_gen = nullptr;      // tables the device generated, one per job of the chunk
@@ -124,6 +128,8 @@ struct nxz_ctx {
 			if (d_wg_ws) (void)hipFree(d_wg_ws);
 			if (d_frame_jobs) (void)hipFree(d_frame_jobs);
 			if (d_bgzf_ws) (void)hipFree(d_bgzf_ws);
+			if (d_rng_ws) (void)hipFree(d_rng_ws);
+			if (d_rng_slots) (void)hipFree(d_rng_slots);
 			if (d_tokens) (void)hipFree(d_tokens);                       // (d_gen and d_counts lie inside it)
 			if (d_cand2) (void)hipFree(d_cand2);
 			if (d_fuse) (void)hipFree(d_fuse);
@@ -982,27 +988,15 @@ extern "C" int nxz_batch_decompress_framed(nxz_ctx_t *c, int fmt, const nxz_batc
 	return framed_locked(c, fmt, jobs, n, results, frames, s);
 }
 
-// A BGZF image in device memory: the members found on the device (nxz_launch_bgzf_discover), then ONE wait for their count,
-// then the framed gzip path on them.
-extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
-				     uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
-				     size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream)
+// The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then
+// ONE wait for ctl = candidates, members, bytes covered, sum of ISIZE.  The caller holds c->frame_use[s].
+static int bgzf_discover_locked(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, size_t max_members,
+				uint64_t *coff, hipStream_t s, uint64_t ctl[4], nxz_batch_job_t **jobs)
 {
-	if (members) *members = 0;
-	if (consumed) *consumed = 0;
-	if (out_len) *out_len = 0;
-	if (!c || (len && !packed) || !offsets || (max_members && (!frames || !results))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (len < 26) return -EILSEQ;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
 	// room for the candidates: twice the members the caller allows, and one every 32 KiB (a true member has at most
 	// 64 KiB); an image with more -- false candidates in the payloads -- is run again with room for all of them
 	const uint64_t most = len / 4 + 1;                                   // (1f 8b 08 04 cannot overlap itself)
 	uint64_t cap = std::min<uint64_t>(most, std::max<uint64_t>((uint64_t)max_members * 2 + 1024, len / 32768 + 1024));
-	uint64_t ctl[4] = {0, 0, 0, 0};
-	nxz_batch_job_t *jobs = nullptr;
 	for (int pass = 0; pass < 2; pass++) {
 		uint8_t *ws = nullptr;
 		{
@@ -1019,13 +1013,36 @@ extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64
 			sc.bgzf_cap = std::max(sc.bgzf_cap, cap);
 			ws = sc.d_bgzf_ws;
 		}
-		int rc = nxz_launch_bgzf_discover(packed, len, dst, offsets, max_members, ws, cap, &jobs, s);
+		int rc = nxz_launch_bgzf_discover(packed, len, dst, offsets, max_members, ws, cap, jobs, s);
+		if (!rc && coff) rc = nxz_launch_bgzf_coff(packed, len, ws, cap, max_members, coff, s);
 		if (rc) { set_err("bgzf discovery launch", (hipError_t)rc); return -EIO; }
-		HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
+		HIPCHK(hipMemcpyAsync(ctl, ws, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s), return -EIO);
 		HIPCHK(hipStreamSynchronize(s), return -EIO);
 		if (ctl[0] <= cap) break;
 		cap = ctl[0];                                                    // (every candidate, the second time)
 	}
+	return 0;
+}
+
+// A BGZF image in device memory: the members found on the device (nxz_launch_bgzf_discover), then ONE wait for their count,
+// then the framed gzip path on them.
+extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
+				     uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
+				     size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream)
+{
+	if (members) *members = 0;
+	if (consumed) *consumed = 0;
+	if (out_len) *out_len = 0;
+	if (!c || (len && !packed) || !offsets || (max_members && (!frames || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (len < 26) return -EILSEQ;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint64_t ctl[4] = {0, 0, 0, 0};
+	nxz_batch_job_t *jobs = nullptr;
+	int rc = bgzf_discover_locked(c, packed, len, dst, offsets, max_members, nullptr, s, ctl, &jobs);
+	if (rc) return rc;
 	const uint64_t L = ctl[1];
 	if (L == 0) return -EILSEQ;
 	if (members) *members = L;
@@ -1034,9 +1051,113 @@ extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64
 	if (out_len) *out_len = ctl[3];
 	if (ctl[3] > dst_cap) return -E2BIG;
 	if (L >= (1u << 31)) return -E2BIG;
-	int rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)L, results, frames, s);
+	rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)L, results, frames, s);
 	if (rc) return rc;
 	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	return 0;
+}
+
+// The member index of a BGZF image: the discovery of nxz_batch_unpack_gzip (its layout's offsets are uoff) and coff.
+extern "C" int nxz_bgzf_index(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint64_t *coff, uint64_t *uoff, size_t max_members,
+			      uint64_t *members, void *stream)
+{
+	if (members) *members = 0;
+	if (!c || (len && !packed) || !coff || !uoff) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (len < 26) return -EILSEQ;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint64_t ctl[4] = {0, 0, 0, 0};
+	nxz_batch_job_t *jobs = nullptr;
+	int rc = bgzf_discover_locked(c, packed, len, nullptr, uoff, max_members, coff, s, ctl, &jobs);
+	if (rc) return rc;
+	if (ctl[1] == 0) return -EILSEQ;
+	if (members) *members = ctl[1];
+	return ctl[1] > max_members ? -E2BIG : 0;
+}
+
+// Members a chunk of nxz_bgzf_read_ranges decodes at most: NXZ_BGZF_CHUNK (read at every call: the tests lower it), 16 384
+static uint64_t bgzf_chunk_members()
+{
+	const char *e = getenv("NXZ_BGZF_CHUNK");
+	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
+	return v && v < 16384 ? v : 16384;
+}
+
+// Ranges of a BGZF image: the map (nxz_bgzf.hip) and ONE wait for its totals, then per chunk of needed members their
+// framed decode into slots and the gather of the pieces, then the zeros of damaged ranges and a last wait.
+extern "C" int nxz_bgzf_read_ranges(nxz_ctx_t *c, const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff,
+				    uint64_t nidx, int kind, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst, uint64_t dst_cap,
+				    uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !coff || !uoff || !offsets || nidx == 0 || nidx > 0xffffffffull || (packed_len && !packed) || (n && (!ranges || !status)) ||
+	    (kind != NXZ_RANGE_UOFF && kind != NXZ_RANGE_VOFF) || n >= (1ull << 31))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t L = nidx - 1;
+	uint8_t *ws = nullptr;
+	{
+		std::lock_guard<std::mutex> g(c->mtx);
+		nxz_ctx::Scratch &sc = c->scratch[s];
+		const size_t need = nxz_bgzf_ranges_workspace(n, L);
+		if (sc.rng_bytes < need) {
+			if (sc.d_rng_ws) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_rng_ws); }
+			sc.d_rng_ws = nullptr; sc.rng_bytes = 0;
+			HIPCHK(hipMalloc((void **)&sc.d_rng_ws, need), return -ENOMEM);
+			sc.rng_bytes = need;
+		}
+		ws = sc.d_rng_ws;
+	}
+	int rc = nxz_launch_bgzf_map(packed, packed_len, coff, uoff, L, kind, ranges, n, offsets, status, ws, s);
+	if (rc) { set_err("bgzf map launch", (hipError_t)rc); return -EIO; }
+	uint64_t ctl[5];
+	HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (ctl[0]) return -EILSEQ;
+	if (out_len) *out_len = ctl[2];
+	if (ctl[2] > dst_cap || (ctl[2] && !dst)) return -E2BIG;
+	const uint64_t needed = ctl[1], pieces = ctl[3];
+	if (!needed) return 0;
+	// a slot per member of the chunk, all of the largest needed member's size (65 536 for BGZF): at most 1 GiB of them
+	const uint64_t stride = (std::max<uint64_t>(ctl[4], 16) + 15) & ~(uint64_t)15;
+	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / stride)));
+	const size_t sb = (per * stride + 255) & ~(size_t)255, jb = (per * sizeof(nxz_batch_job_t) + 255) & ~(size_t)255,
+		     fb = (per * sizeof(nxz_batch_frame_t) + 255) & ~(size_t)255;
+	uint8_t *slots = nullptr;
+	{
+		std::lock_guard<std::mutex> g(c->mtx);
+		nxz_ctx::Scratch &sc = c->scratch[s];
+		const size_t need = sb + jb + fb + per * sizeof(nxz_batch_result_t);
+		if (sc.slots_bytes < need) {
+			if (sc.d_rng_slots) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_rng_slots); }
+			sc.d_rng_slots = nullptr; sc.slots_bytes = 0;
+			HIPCHK(hipMalloc((void **)&sc.d_rng_slots, need), return -ENOMEM);
+			sc.slots_bytes = need;
+		}
+		slots = sc.d_rng_slots;
+	}
+	nxz_batch_job_t *jobs = (nxz_batch_job_t *)(slots + sb);
+	nxz_batch_frame_t *frames = (nxz_batch_frame_t *)(slots + sb + jb);
+	nxz_batch_result_t *results = (nxz_batch_result_t *)(slots + sb + jb + fb);
+	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
+		const uint64_t cnt = std::min(per, needed - k0);
+		rc = nxz_launch_bgzf_jobs(packed, coff, uoff, n, L, ws, k0, cnt, slots, stride, jobs, s);
+		if (rc) { set_err("bgzf jobs launch", (hipError_t)rc); return -EIO; }
+		rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)cnt, results, frames, s);
+		if (rc) return rc;
+		rc = nxz_launch_bgzf_gather(uoff, n, L, pieces, ws, offsets, slots, stride, k0, cnt, frames, results, dst, status, s);
+		if (rc) { set_err("bgzf gather launch", (hipError_t)rc); return -EIO; }
+	}
+	rc = nxz_launch_bgzf_zero(n, offsets, status, dst, s);
+	if (rc) { set_err("bgzf zero launch", (hipError_t)rc); return -EIO; }
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (decoded) *decoded = needed;
 	return 0;
 }
 

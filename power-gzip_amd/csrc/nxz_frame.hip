@@ -292,6 +292,15 @@ __global__ __launch_bounds__(1024) void layout_kernel(const uint8_t *__restrict_
 	if (t == 1023) { offsets[L] = part[1023]; ctl[3] = part[1023]; }
 }
 
+// coff[j] = where member j starts, coff[L] = the bytes the members cover (nxz_bgzf_index; uoff is layout_kernel's offsets)
+__global__ __launch_bounds__(256) void coff_kernel(const uint64_t *__restrict__ pos, const uint64_t *__restrict__ ctl, uint64_t max_members,
+						   const uint32_t *__restrict__ memb, uint64_t *__restrict__ coff)
+{
+	const uint64_t L = ctl[1], j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+	if (L == 0 || L > max_members || j > L) return;
+	coff[j] = j < L ? pos[memb[j]] : ctl[2];
+}
+
 } // namespace nxzf
 
 extern "C" int nxz_launch_frame_header(int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames, nxz_batch_job_t *derived, hipStream_t stream)
@@ -318,22 +327,42 @@ extern "C" size_t nxz_bgzf_workspace(uint64_t len, uint64_t cap)
 	       up256(cap * sizeof(nxz_batch_job_t));
 }
 
+// The discovery's arrays inside ws (nxz_launch_bgzf_discover, nxz_launch_bgzf_coff)
+struct BgzfWs {
+	uint64_t *ctl, *pos;
+	uint32_t *tile_cnt, *tile_off, *size, *memb, *isz, *J;
+	nxz_batch_job_t *jobs;
+	uint64_t tiles;
+	uint32_t levels;
+};
+static BgzfWs bgzf_ws(uint8_t *ws, const uint8_t *packed, uint64_t len, uint64_t cap)
+{
+	BgzfWs w;
+	w.tiles = (len + ((uintptr_t)packed & 15) + nxzf::TILE - 1) / nxzf::TILE;
+	w.levels = bgzf_levels(cap);
+	uint8_t *p = ws;
+	auto take = [&](size_t b) { uint8_t *q = p; p += up256(b); return q; };
+	w.ctl = (uint64_t *)take(4 * sizeof(uint64_t));
+	w.tile_cnt = (uint32_t *)take(w.tiles * 4 + 4); w.tile_off = (uint32_t *)take(w.tiles * 4 + 4);
+	w.pos = (uint64_t *)take(cap * 8);
+	w.size = (uint32_t *)take(cap * 4); w.memb = (uint32_t *)take(cap * 4); w.isz = (uint32_t *)take(cap * 4);
+	w.J = (uint32_t *)take((size_t)w.levels * (cap + 1) * 4);
+	w.jobs = (nxz_batch_job_t *)take(cap * sizeof(nxz_batch_job_t));
+	return w;
+}
+
 // Finds the members of the image and lays them out.  ws[0..3] (uint64, device): candidates, members L, bytes covered, sum of ISIZE.
 // When L <= max_members: offsets[0..L] and *jobs (inside ws) are written.  When candidates > cap, the chain is not complete:
 // the caller grows cap to the count and runs it again.
 extern "C" int nxz_launch_bgzf_discover(const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, uint64_t max_members, uint8_t *ws,
 					uint64_t cap, nxz_batch_job_t **jobs, hipStream_t stream)
 {
-	const uint64_t tiles = (len + ((uintptr_t)packed & 15) + nxzf::TILE - 1) / nxzf::TILE;
-	const uint32_t levels = bgzf_levels(cap);
-	uint8_t *p = ws;
-	auto take = [&](size_t b) { uint8_t *q = p; p += up256(b); return q; };
-	uint64_t *ctl = (uint64_t *)take(4 * sizeof(uint64_t));
-	uint32_t *tile_cnt = (uint32_t *)take(tiles * 4 + 4), *tile_off = (uint32_t *)take(tiles * 4 + 4);
-	uint64_t *pos = (uint64_t *)take(cap * 8);
-	uint32_t *size = (uint32_t *)take(cap * 4), *memb = (uint32_t *)take(cap * 4), *isz = (uint32_t *)take(cap * 4);
-	uint32_t *J = (uint32_t *)take((size_t)levels * (cap + 1) * 4);
-	*jobs = (nxz_batch_job_t *)take(cap * sizeof(nxz_batch_job_t));
+	const BgzfWs w = bgzf_ws(ws, packed, len, cap);
+	const uint64_t tiles = w.tiles;
+	const uint32_t levels = w.levels;
+	uint64_t *ctl = w.ctl, *pos = w.pos;
+	uint32_t *tile_cnt = w.tile_cnt, *tile_off = w.tile_off, *size = w.size, *memb = w.memb, *isz = w.isz, *J = w.J;
+	*jobs = w.jobs;
 	(void)hipMemsetAsync(ctl, 0, 4 * sizeof(uint64_t), stream);
 	if (tiles == 0 || tiles >= (1ull << 31)) return tiles ? (int)hipErrorInvalidValue : 0;
 	hipLaunchKernelGGL(nxzf::bgzf_scan_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, packed, len, tile_cnt, nullptr, cap, nullptr, nullptr);
@@ -347,5 +376,16 @@ extern "C" int nxz_launch_bgzf_discover(const uint8_t *packed, uint64_t len, uin
 	hipLaunchKernelGGL(nxzf::chain_kernel, dim3(1), dim3(1), 0, stream, pos, size, ctl, cap, J, levels);
 	hipLaunchKernelGGL(nxzf::member_kernel, dim3(g), dim3(256), 0, stream, packed, pos, size, ctl, cap, J, levels, max_members, memb, isz);
 	hipLaunchKernelGGL(nxzf::layout_kernel, dim3(1), dim3(1024), 0, stream, packed, pos, size, ctl, max_members, memb, isz, dst, offsets, *jobs);
+	return (int)hipGetLastError();
+}
+
+
+// After nxz_launch_bgzf_discover on the same ws, len and cap: coff[0..L] when 0 < L <= max_members
+extern "C" int nxz_launch_bgzf_coff(const uint8_t *packed, uint64_t len, uint8_t *ws, uint64_t cap, uint64_t max_members, uint64_t *coff,
+				    hipStream_t stream)
+{
+	const BgzfWs w = bgzf_ws(ws, packed, len, cap);
+	const uint64_t most = (max_members < cap ? max_members : cap) + 1;
+	hipLaunchKernelGGL(nxzf::coff_kernel, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, stream, w.pos, w.ctl, max_members, w.memb, coff);
 	return (int)hipGetLastError();
 }

@@ -4,6 +4,7 @@ Fails loudly when the shared library is missing or no gfx950 device is present: 
 no CPU fallback on the product path.
 """
 import ctypes as C
+import errno
 import os
 
 import numpy as np
@@ -40,6 +41,10 @@ FRAME_DTYPE = np.dtype([("status", "<u4"), ("format", "<u4"), ("hdr_len", "<u4")
                         ("isize", "<u4"), ("mtime", "<u4"), ("dictid", "<u4"), ("extra_off", "<u4"), ("extra_len", "<u4"),
                         ("name_off", "<u4"), ("comment_off", "<u4"), ("flg", "u1"), ("xfl", "u1"), ("os", "u1"), ("cinfo", "u1")])
 assert FRAME_DTYPE.itemsize == 52
+
+# BGZF random access (include/nxz_engine.h: nxz_bgzf_index / nxz_bgzf_read_ranges)
+RANGE_UOFF, RANGE_VOFF = 0, 1
+RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED = range(4)
 
 
 class StreamResume(C.Structure):
@@ -87,6 +92,10 @@ def load_library():
         L.nxz_batch_decompress_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
+        L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
+        L.nxz_bgzf_read_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_inflate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -227,6 +236,42 @@ class Engine:
                                           C.byref(out_len), self.stream_handle())
         return rc, {"members": members.value, "consumed": consumed.value, "out_len": out_len.value,
                     "offsets": offsets, "frames": frames, "results": results}
+
+    def bgzf_index(self, packed, length, max_members):
+        """the member index of a BGZF image (uint8 device tensor, `length` bytes from its start), nxz_bgzf_index.
+        Returns (coff, uoff): int64 device tensors of members + 1 entries.  Raises EngineError on -EILSEQ / -E2BIG."""
+        t = self.torch
+        coff = t.empty(max_members + 1, dtype=t.int64, device=self.dev)
+        uoff = t.empty(max_members + 1, dtype=t.int64, device=self.dev)
+        members = C.c_uint64()
+        rc = self.L.nxz_bgzf_index(self.ctx, packed.data_ptr(), length, coff.data_ptr(), uoff.data_ptr(), max_members, C.byref(members),
+                                   self.stream_handle())
+        self._check(rc, "nxz_bgzf_index")
+        return coff[:members.value + 1], uoff[:members.value + 1]
+
+    def bgzf_read_ranges(self, packed, length, coff, uoff, ranges, kind=RANGE_UOFF, dst=None):
+        """ranges of a BGZF image through its index (coff / uoff: int64 device tensors, a slice of an index with `packed` holding
+        the image from coff[0] on), nxz_bgzf_read_ranges.  ranges: (n, 2) int64 device tensor of [begin, end).  dst: uint8
+        device tensor (None: room for the bytes asked for).  Returns (rc, offsets, status, out_len, decoded, dst): rc 0 /
+        -errno, offsets (n + 1) int64 and status (n) int32 device tensors."""
+        t = self.torch
+        n = ranges.shape[0]
+        offsets = t.zeros(n + 1, dtype=t.int64, device=self.dev)
+        status = t.zeros(max(n, 1), dtype=t.int32, device=self.dev)
+        out_len, decoded = C.c_uint64(), C.c_uint64()
+        if dst is None:                  # (a first call for the size; the second call runs the map again)
+            rc = self._read_ranges(packed, length, coff, uoff, ranges, kind, None, 0, offsets, status, out_len, decoded)
+            dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
+            if rc != -errno.E2BIG:
+                return rc, offsets, status[:n], out_len.value, decoded.value, dst
+        rc = self._read_ranges(packed, length, coff, uoff, ranges, kind, dst, dst.numel(), offsets, status, out_len, decoded)
+        return rc, offsets, status[:n], out_len.value, decoded.value, dst
+
+    def _read_ranges(self, packed, length, coff, uoff, ranges, kind, dst, cap, offsets, status, out_len, decoded):
+        assert coff.numel() == uoff.numel() and ranges.is_contiguous() and ranges.dtype == self.torch.int64
+        return self.L.nxz_bgzf_read_ranges(self.ctx, packed.data_ptr(), length, coff.data_ptr(), uoff.data_ptr(), coff.numel(), kind,
+                                           ranges.data_ptr(), ranges.shape[0], dst.data_ptr() if dst is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
+                                           C.byref(out_len), C.byref(decoded), self.stream_handle())
 
     def pack_gzip(self, jobs, results, n, packed, offsets=None):
         """BGZF members from a compress batch, nxz_batch_pack_gzip.  Returns the offsets (int64 device tensor, n + 1)."""
