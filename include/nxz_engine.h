@@ -215,7 +215,7 @@ typedef struct nxz_batch_job {
 	uint32_t       dht_index; /* DHT jobs: which table of the batch's dht array */
 	uint32_t       resume;    /* decompress resume state: in_rembytecnt | in_sfbt << 16 | in_subc << 20
 				   * (0 = start at a block header on a byte boundary, FC 0x10) */
-	uint32_t       reserved;  /* flags, additive: NXZ_JOB_SUSPEND_WHEN_FULL */
+	uint32_t       reserved;  /* flags, additive: NXZ_JOB_SUSPEND_WHEN_FULL, NXZ_JOB_NO_DICT */
 } nxz_batch_job_t;
 
 /* Decompress jobs (additive; the reference's engine has no such thing and its library runs a job
@@ -387,7 +387,7 @@ enum {
 	NXZ_FRAME_OK = 0,
 	NXZ_FRAME_BAD_HEADER,    /* gzip ID1 ID2 / reserved FLG bits; zlib FCHECK / CINFO > 7; a job with resume or hist_len set */
 	NXZ_FRAME_BAD_METHOD,    /* CM != 8 */
-	NXZ_FRAME_NEED_DICT,     /* zlib FDICT: preset dictionaries are not supported, nothing is decoded (dictid is set) */
+	NXZ_FRAME_NEED_DICT,     /* zlib FDICT and the call holds no dictionary of that DICTID (nxz_batch_decompress_framed: none at all): nothing is decoded (dictid is set) */
 	NXZ_FRAME_BAD_HCRC,      /* gzip FHCRC does not match the header */
 	NXZ_FRAME_TRUNCATED,     /* the source ends inside the header, the deflate data or the trailer */
 	NXZ_FRAME_DEFLATE,       /* the deflate data failed: results[i].cc says why */
@@ -434,6 +434,59 @@ int nxz_batch_decompress_framed(nxz_ctx_t *ctx, int fmt, const nxz_batch_job_t *
 int nxz_batch_unpack_gzip(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
 			  uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
 			  size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream);
+
+/* ------------------------------------------------------------------------
+ * One preset dictionary for all jobs of a batch (zlib's deflateSetDictionary / inflateSetDictionary)
+ * ---------------------------------------------------------------------- */
+/* `len` HOST bytes (any length, 0 = no dictionary: the _dict calls then give what their plain counterparts give).  The object
+ * owns a 16-byte aligned device copy; it is immutable and may be used by many streams and threads at once; destroy it when
+ * no call that uses it is still running.  The rules (power-gzip_amd/csrc/nxz_dict.h):
+ *   inflate window: the last min(len, 32768) bytes, what zlib's inflateSetDictionary keeps;
+ *   deflate window: the last W = min(len, 32768) & ~15 bytes (the compress kernels' histories are multiples of 16; the up to
+ *   15 leading bytes are never referred to).  A compress job carries at most 65536 - W bytes.
+ * 0 or a negative errno. */
+typedef struct nxz_dict nxz_dict_t;
+int      nxz_dict_create(nxz_ctx_t *ctx, const uint8_t *bytes, size_t len, nxz_dict_t **out);
+void     nxz_dict_destroy(nxz_ctx_t *ctx, nxz_dict_t *d);
+uint32_t nxz_dict_id(const nxz_dict_t *d);       /* Adler-32 of all len bytes from 1: zlib's DICTID */
+
+/* jobs[].reserved, honoured by the _dict calls only: this job sees no dictionary */
+#define NXZ_JOB_NO_DICT 2u
+
+/* nxz_batch_compress with the dictionary's deflate window as every job's history: jobs[i].src is the source alone, hist_len
+ * must be 0.  dst, results[i] and counts are bit for bit what nxz_batch_compress gives for the job [deflate window][source]
+ * with hist_len = W -- except spbc, which counts the source bytes only.  The streams inflate with
+ * zlib's inflateSetDictionary(the whole dictionary), or nxz_batch_decompress_dict.  The window is read from the one device
+ * copy (no staging per job).  A job with hist_len != 0 or W + src_len > 65536: cc = NXZ_CC_INVALID_OP, tpbc = 0, dst untouched.
+ * Every fc of nxz_batch_compress (the RESUME bit is implied).  Asynchronous on `stream`. */
+int nxz_batch_compress_dict(nxz_ctx_t *ctx, int fc, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+			    const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results, uint32_t *counts, void *stream);
+
+/* Raw deflate streams whose distances may reach into the dictionary's inflate window: output and results[i] are what
+ * nxz_batch_decompress gives for the job [inflate window][stream] with hist_len = window, failures included (a distance in
+ * front of the window: NXZ_CC_INVALID_DIST) -- except spbc, which counts the stream's bytes only.  resume and hist_len must be 0
+ * (else NXZ_CC_INVALID_OP, dst untouched).  Streams of NXZ_DICT_WG_MIN (environment, default 4096) source bytes or more go a
+ * workgroup each with the window preloaded into LDS; what that kernel hands back (errors, early ends, small targets, dst not
+ * 16-byte aligned) and every smaller stream goes a wavefront each and reads the window from the device copy -- the choice is made
+ * on the device, job by job.  nxz_ctx_wg_reasons reports on the workgroup launch.  Asynchronous on `stream`, no host wait.
+ * Speed (profiles/r08_dict.txt): streams of less than about 4 KiB run at 0.9 - 1.0 x of what nxz_batch_decompress makes of jobs
+ * staged as [window][stream] per job -- the call saves their memory, not time --, streams of 16 - 32 KiB of output 1.1 - 1.6 x.
+ * A source that is not 16-byte aligned gets a quarter of the bound (it costs the wavefront kernel more). */
+int nxz_batch_decompress_dict(nxz_ctx_t *ctx, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+			      nxz_batch_result_t *results, void *stream);
+
+/* nxz_batch_pack_zlib for streams made by nxz_batch_compress_dict: FDICT set, FCHECK to match, DICTID (4 bytes, big-endian)
+ * behind FLG -- the header zlib's deflate writes after deflateSetDictionary; for an empty dictionary still FDICT, DICTID 1.
+ * `packed` needs n * 10 + sum(max(tpbc, length + 5)) bytes at most. */
+int nxz_batch_pack_zlib_dict(nxz_ctx_t *ctx, int level, const nxz_dict_t *dict, const nxz_batch_job_t *jobs,
+			     const nxz_batch_result_t *results, size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
+
+/* nxz_batch_decompress_framed for a caller that holds a dictionary: a zlib job with FDICT and DICTID == nxz_dict_id(dict) is
+ * decoded with it (NXZ_FRAME_OK, hdr_len 6, dictid reported); another DICTID: NXZ_FRAME_NEED_DICT, nothing decoded.  A zlib job
+ * without FDICT and every gzip job is decoded WITHOUT the dictionary, so a stream that refers to it anyway fails as in zlib.
+ * One batch may mix all of these. */
+int nxz_batch_decompress_framed_dict(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
 
 /* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads

@@ -117,6 +117,19 @@ size_t nxz_inflate_wg_workspace(size_t n);
 int nxz_launch_inflate_wg(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io,
 			  uint8_t *wg_ws, const uint32_t *order, uint8_t *const *targets, hipStream_t stream);   /* targets (may be NULL): the outputs there too, in the checksum pass */
 int nxz_launch_cksum_copy(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint8_t *const *targets, hipStream_t stream);
+/* one preset dictionary for all jobs of a batch (nxz_dict.h; the nxz_batch_*_dict calls) */
+int nxz_launch_dict_jobs(const nxz_batch_job_t *in, size_t n, uint32_t W, nxz_batch_job_t *out, hipStream_t stream);          /* the caller's jobs with the deflate window "in front" */
+int nxz_launch_dict_finish(const nxz_batch_job_t *in, size_t n, uint32_t W, nxz_batch_result_t *results, hipStream_t stream); /* the jobs that were not taken: NXZ_CC_INVALID_OP */
+int nxz_launch_lz77_dict(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
+			 uint32_t *counts, uint32_t *job_counter, const uint8_t *dict, hipStream_t stream);
+int nxz_launch_inflate_wg_dict(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint8_t *wg_ws, const uint32_t *order,
+			       const uint8_t *dwin, uint32_t dlen, uint32_t src_min, hipStream_t stream);   /* dwin: 32 KiB, its last dlen bytes the inflate window; streams below src_min source bytes: a wavefront each */
+int nxz_launch_inflate_order_only_dict(const nxz_batch_job_t *jobs, size_t nslots, nxz_batch_result_t *results, const uint32_t *order,
+				       const uint8_t *dict_end, uint32_t dlen, uint32_t src_below, hipStream_t stream);
+int nxz_launch_pack_zlib_dict(const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n, uint32_t flg, uint32_t dictid,
+			      uint64_t *offsets, uint8_t *packed, hipStream_t stream);
+int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames, nxz_batch_job_t *derived,
+				 uint32_t dictid, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

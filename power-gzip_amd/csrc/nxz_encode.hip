@@ -127,6 +127,7 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 	const uint32_t total = job.src_len;
 	const uint32_t h = job.hist_len < total ? job.hist_len : total;
 	const uint32_t n = total - h;
+	// (the source alone: for the jobs of nxz_batch_compress_dict -- nxzl77::dict_jobs_kernel -- the h bytes below it are NOT memory of the caller's)
 	const uint8_t NXZ_GLOBAL_AS *src = (const uint8_t NXZ_GLOBAL_AS *)job.src + h;
 	const uint8_t NXZ_GLOBAL_AS *tk = (const uint8_t NXZ_GLOBAL_AS *)tokens_ + (size_t)bid * NXZ_TOK_STRIDE;
 	const uint32_t NXZ_GLOBAL_AS *litb = (const uint32_t NXZ_GLOBAL_AS *)(tk + NXZ_TOK_LITBITS);

@@ -23,8 +23,10 @@
 #include <map>
 #include <deque>
 #include <mutex>
+#include <new>
 #include <vector>
 #include "nxz_device.h"
+#include "nxz_dict.h"
 #include "../../include/nxz_wire.h"
 
 #define NXZ_VERSION "nxz-engine 0.1 (gfx950)"
@@ -87,6 +89,8 @@ struct nxz_ctx {
 		size_t wg_cap = 0;
 		nxz_batch_job_t *d_frame_jobs = nullptr;  // nxz_batch_decompress_framed: the derived raw jobs (the deflate bytes of each stream)
 		size_t frame_cap = 0;
+		nxz_batch_job_t *d_dict_jobs = nullptr;   // nxz_batch_compress_dict: the caller's jobs with the dictionary's window "in front"
+		size_t dict_jobs_cap = 0;
 		uint8_t *d_bgzf_ws = nullptr;             // nxz_batch_unpack_gzip: the discovery's candidates, jump tables and the members' jobs
 		size_t bgzf_bytes = 0;
 		uint64_t bgzf_cap = 0;                    // ... candidates it has room for
@@ -127,6 +131,7 @@ struct nxz_ctx {
 			if (d_cut_ws) (void)hipFree(d_cut_ws);
 			if (d_wg_ws) (void)hipFree(d_wg_ws);
 			if (d_frame_jobs) (void)hipFree(d_frame_jobs);
+			if (d_dict_jobs) (void)hipFree(d_dict_jobs);
 			if (d_bgzf_ws) (void)hipFree(d_bgzf_ws);
 			if (d_rng_ws) (void)hipFree(d_rng_ws);
 			if (d_rng_slots) (void)hipFree(d_rng_slots);
@@ -232,6 +237,7 @@ static constexpr unsigned JOB_COUNTERS = 256;
 #define NXZ_LANES_MIN 49152
 #define NXZ_LANES_TABLES_MIN 163840   /* streams that bring tables: the lane kernel from here on */
 #define NXZ_WINDOW_LDS_MAX 1024
+#define NXZ_DICT_WG_MIN_DEFAULT 4096    /* nxz_batch_decompress_dict: source bytes from which a stream goes a workgroup each (profiles/r08_dict.txt: the two routes break even at about 4 KiB of source, 10 KiB of output) */
 
 static std::mutex g_mtx;
 static nxz_ctx *g_ctx[64];
@@ -418,12 +424,67 @@ static size_t compress_chunk(size_t n)
 	return c;
 }
 
+// A preset dictionary (nxz_dict.h): ONE device buffer of 32 KiB whose last `win` bytes are the inflate window; the deflate
+// window is its last W bytes (W a multiple of 16, the buffer's end 16-byte aligned: so is the window).
+struct nxz_dict {
+	int device = 0;
+	size_t len = 0;
+	uint32_t id = 1, win = 0, W = 0;
+	uint8_t *d_win = nullptr;
+	const uint8_t *deflate_window() const { return d_win + NXZ_DICT_WINDOW - W; }
+};
+
+extern "C" int nxz_dict_create(nxz_ctx_t *c, const uint8_t *bytes, size_t len, nxz_dict_t **out)
+{
+	if (!c || !out || (len && !bytes)) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	nxz_dict *d = new (std::nothrow) nxz_dict;
+	if (!d) return -ENOMEM;
+	d->device = c->device; d->len = len;
+	d->id = nxz_dict_adler32(bytes, len);
+	d->win = nxz_dict_inflate_window(len); d->W = nxz_dict_deflate_window(len);
+	std::vector<uint8_t> img(NXZ_DICT_WINDOW, 0);
+	if (d->win) memcpy(img.data() + NXZ_DICT_WINDOW - d->win, bytes + nxz_dict_inflate_start(len), d->win);
+	if (hipMalloc((void **)&d->d_win, NXZ_DICT_WINDOW) != hipSuccess) { (void)hipGetLastError(); delete d; return -ENOMEM; }
+	hipError_t e = hipMemcpy(d->d_win, img.data(), NXZ_DICT_WINDOW, hipMemcpyHostToDevice);
+	if (e != hipSuccess) { set_err("dictionary copy", e); (void)hipFree(d->d_win); delete d; return -EIO; }
+	*out = d;
+	return 0;
+}
+extern "C" void nxz_dict_destroy(nxz_ctx_t *c, nxz_dict_t *d)
+{
+	if (!d) return;
+	if (!forked_child()) { (void)hipSetDevice(d->device); (void)hipFree(d->d_win); }
+	delete d;
+}
+extern "C" uint32_t nxz_dict_id(const nxz_dict_t *d) { return d ? d->id : 1; }
+
 // The compress function codes: LZ77 kernel (tokens, counts, checksums) -> [table generator] ->
 // entropy kernel, chunk after chunk on the caller's stream.
+static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *jobs, size_t n,
+			  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
+			  uint32_t *counts, void *stream, const nxz_dict *dict);
 extern "C" int nxz_batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *jobs, size_t n,
 				  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
 				  uint32_t *counts, void *stream)
 {
+	return batch_compress(c, fc, jobs, n, dht, ntables, results, counts, stream, nullptr);
+}
+// ... with one dictionary as every job's window: the kernels get the caller's jobs rewritten on the device (nxz_launch_dict_jobs:
+// 48 bytes a job of per-stream scratch, no copy of the window), the LZ77 kernel's load phase takes the window from the dictionary
+extern "C" int nxz_batch_compress_dict(nxz_ctx_t *c, int fc, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+				       const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
+				       uint32_t *counts, void *stream)
+{
+	if (!c || !dict || dict->device != c->device || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
+	return batch_compress(c, fc, jobs, n, dht, ntables, results, counts, stream, dict);
+}
+static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, size_t n,
+			  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
+			  uint32_t *counts, void *stream, const nxz_dict *dict)
+{
+	const nxz_batch_job_t *jobs = ujobs;
 	if (!c || !nxz_fc_is_compress((uint32_t)fc) || (fc & 1) || (fc & ~0x2e)) return -EINVAL;
 	if (forked_child()) return -ENODEV;
 	const bool gen = nxz_fc_is_dhtgen((uint32_t)fc);
@@ -494,7 +555,18 @@ extern "C" int nxz_batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *j
 			r.prepared_cap = ntables;
 		}
 		if (!c->d_job_counters && hipMalloc((void **)&c->d_job_counters, JOB_COUNTERS * sizeof(uint32_t)) != hipSuccess) c->d_job_counters = nullptr;
+		if (dict && r.dict_jobs_cap < n) {
+			if (r.d_dict_jobs) { (void)hipStreamSynchronize(s); (void)hipFree(r.d_dict_jobs); }
+			r.d_dict_jobs = nullptr; r.dict_jobs_cap = 0;
+			HIPCHK(hipMalloc((void **)&r.d_dict_jobs, n * sizeof(nxz_batch_job_t)), return -ENOMEM);
+			r.dict_jobs_cap = n;
+		}
 		sc = r;
+	}
+	if (dict) {
+		int rc = nxz_launch_dict_jobs(ujobs, n, dict->W, sc.d_dict_jobs, s);
+		if (rc) { set_err("dictionary jobs launch", (hipError_t)rc); return -EIO; }
+		jobs = sc.d_dict_jobs;
 	}
 	if (isdht && !gen) {
 		prepared = sc.d_prepared;
@@ -518,7 +590,9 @@ extern "C" int nxz_batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *j
 			c->tev.push_back(e);
 		};
 		stamp();
-		int rc = fused_gen ? nxz_launch_lz77(NXZ_LZ77_FUSED_GEN, jobs + off, m, sc.d_fuse, sc.d_cand2, results + off, count ? counts + off * 316 : nullptr, jc, s)
+		int rc = dict ? (fused_gen ? nxz_launch_lz77_dict(NXZ_LZ77_FUSED_GEN, jobs + off, m, sc.d_fuse, sc.d_cand2, results + off, count ? counts + off * 316 : nullptr, jc, dict->deflate_window(), s)
+					   : nxz_launch_lz77_dict(fused ? NXZ_LZ77_FUSED_FHT : cnt != nullptr, jobs + off, m, sc.d_tokens, sc.d_cand2, results + off, cnt, jc, dict->deflate_window(), s))
+		       : fused_gen ? nxz_launch_lz77(NXZ_LZ77_FUSED_GEN, jobs + off, m, sc.d_fuse, sc.d_cand2, results + off, count ? counts + off * 316 : nullptr, jc, s)
 				   : nxz_launch_lz77(fused ? NXZ_LZ77_FUSED_FHT : cnt != nullptr, jobs + off, m, sc.d_tokens, sc.d_cand2, results + off, cnt, jc, s);
 		if (rc) { set_err("lz77 launch", (hipError_t)rc); return -EIO; }
 		stamp();
@@ -531,6 +605,10 @@ extern "C" int nxz_batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *j
 		rc = nxz_launch_encode(isdht, gen, jobs + off, m, sc.d_tokens, gen ? sc.d_gen : prepared, results + off, s);
 		if (rc) { set_err("encode launch", (hipError_t)rc); return -EIO; }
 		stamp();
+	}
+	if (dict) {
+		int rc = nxz_launch_dict_finish(ujobs, n, dict->W, results, s);
+		if (rc) { set_err("dictionary finish launch", (hipError_t)rc); return -EIO; }
 	}
 	return 0;
 }
@@ -850,6 +928,54 @@ static int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n,
 	return 0;
 }
 
+// Streams that share a preset dictionary: a workgroup each with the window preloaded (nxzw::inflate_wg_dict_kernel), the hand-backs a
+// wavefront each behind it (nxzi::inflate_dict_kernel), checksums -- all on `s`, nothing waits.  The caller holds no lock.
+static int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s)
+{
+	std::mutex *use_mtx;
+	{
+		std::lock_guard<std::mutex> g(c->mtx);
+		use_mtx = &c->scratch_use[s];
+	}
+	std::lock_guard<std::mutex> use(*use_mtx);                     // (one call at a time per stream's scratch)
+	uint8_t *wws = nullptr, *ows = nullptr;
+	{
+		std::lock_guard<std::mutex> g(c->mtx);
+		nxz_ctx::Scratch &sc = c->scratch[s];
+		const size_t need = nxz_inflate_wg_workspace(n), oneed = n >= 128 ? nxz_order_workspace(n) : 0;
+		if (sc.wg_cap < need) {
+			if (sc.d_wg_ws) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_wg_ws); }
+			sc.d_wg_ws = nullptr; sc.wg_cap = 0;
+			HIPCHK(hipMalloc((void **)&sc.d_wg_ws, need), return -ENOMEM);
+			sc.wg_cap = need;
+		}
+		if (sc.order_cap < oneed) {
+			if (sc.d_order_ws) { (void)hipStreamSynchronize(s); (void)hipFree(sc.d_order_ws); }
+			sc.d_order_ws = nullptr; sc.order_cap = 0;
+			if (hipMalloc((void **)&sc.d_order_ws, oneed) == hipSuccess) sc.order_cap = oneed; else (void)hipGetLastError();
+		}
+		wws = sc.d_wg_ws;
+		ows = oneed && sc.order_cap >= oneed ? sc.d_order_ws : nullptr;
+	}
+	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;
+	// Streams of fewer than NXZ_DICT_WG_MIN source bytes go a wavefront each from the start: the workgroup kernel costs a stream 84 000 -
+	// 95 000 cycles whatever its size and has one stream a CU in flight, the wavefront kernel twenty (profiles/r08_dict.txt).  0: all a workgroup each.
+	const char *wm = getenv("NXZ_DICT_WG_MIN");                         // (read at every call: the tests switch it)
+	const uint32_t src_min = wm ? (uint32_t)strtoul(wm, nullptr, 0) : (uint32_t)NXZ_DICT_WG_MIN_DEFAULT;
+	int rc = nxz_launch_inflate_wg_dict(jobs, n, results, wws, order, dict->d_win, dict->win, src_min, s);
+	if (rc) { set_err("inflate launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+extern "C" int nxz_batch_decompress_dict(nxz_ctx_t *c, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+					 nxz_batch_result_t *results, void *stream)
+{
+	if (!c || !dict || dict->device != c->device || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	return batch_decompress_dict(c, dict, jobs, n, results, (hipStream_t)stream);
+}
+
 // (diagnostic / tests: how many streams of the last batch of n that `stream` ran through the lane kernels the fixed-code-only
 // kernel handed back to the general one; waits for the stream)
 extern "C" int nxz_inflate_lanes_handed_back(const uint8_t *workspace, size_t n, uint32_t *count);
@@ -941,12 +1067,22 @@ extern "C" int nxz_batch_pack_zlib(nxz_ctx_t *c, int level, const nxz_batch_job_
 	return 0;
 }
 
+extern "C" int nxz_batch_pack_zlib_dict(nxz_ctx_t *c, int level, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
+					size_t n, uint64_t *offsets, uint8_t *packed, void *stream)
+{
+	if (!c || !dict || dict->device != c->device || !jobs || !results || !offsets || !packed || n > 0xffffffffu || level < -1 || level > 9) return -EINVAL;
+	(void)hipSetDevice(c->device);
+	int rc = nxz_launch_pack_zlib_dict(jobs, results, n, nxz_zlib_cmf_flg(level, 1) & 0xff, dict->id, offsets, packed, (hipStream_t)stream);
+	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
 // The caller holds c->frame_use[s].
 // ---------------------------------------------------------------------------
 static int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
-			 nxz_batch_frame_t *frames, hipStream_t s)
+			 nxz_batch_frame_t *frames, hipStream_t s, const nxz_dict *dict = nullptr)
 {
 	nxz_batch_job_t *derived = nullptr;
 	{
@@ -961,9 +1097,9 @@ static int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, siz
 		}
 		derived = sc.d_frame_jobs;
 	}
-	int rc = nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
+	int rc = dict ? nxz_launch_frame_header_dict(fmt, jobs, n, frames, derived, dict->id, s) : nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
 	if (rc) { set_err("frame header launch", (hipError_t)rc); return -EIO; }
-	rc = batch_decompress(c, derived, n, results, nullptr, s, 0);
+	rc = dict ? batch_decompress_dict(c, dict, derived, n, results, s) : batch_decompress(c, derived, n, results, nullptr, s, 0);
 	if (rc) return rc;
 	rc = nxz_launch_frame_trailer(jobs, n, results, frames, s);
 	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
@@ -986,6 +1122,18 @@ extern "C" int nxz_batch_decompress_framed(nxz_ctx_t *c, int fmt, const nxz_batc
 	hipStream_t s = (hipStream_t)stream;
 	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
 	return framed_locked(c, fmt, jobs, n, results, frames, s);
+}
+
+extern "C" int nxz_batch_decompress_framed_dict(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || !dict || dict->device != c->device || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	return framed_locked(c, fmt, jobs, n, results, frames, s, dict);
 }
 
 // The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then

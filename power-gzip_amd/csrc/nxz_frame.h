@@ -139,6 +139,24 @@ NXZ_HD inline uint32_t nxz_frame_parse(const uint8_t *p, uint32_t len, int fmt, 
 	return st;
 }
 
+// The same for a caller that holds a preset dictionary (nxz_batch_decompress_framed_dict): a zlib header with FDICT whose
+// DICTID is the dictionary's is no fault -- the deflate data starts behind the six bytes and may refer to the dictionary
+// (*use_dict = true).  Any other DICTID, or no dictionary (have_dict false), stays NXZ_FRAME_NEED_DICT; a zlib stream
+// without FDICT and every gzip stream is decoded without the dictionary, as zlib does.
+template <class Ops>
+NXZ_HD inline uint32_t nxz_frame_parse_dict(const uint8_t *p, uint32_t len, int fmt, nxz_batch_frame_t *f, Ops &ops,
+					    bool have_dict, uint32_t dictid, bool *use_dict)
+{
+	uint32_t st = nxz_frame_parse(p, len, fmt, f, ops);
+	*use_dict = false;
+	if (st == NXZ_FRAME_NEED_DICT && have_dict && f->dictid == dictid) {
+		st = NXZ_FRAME_OK;
+		f->status = st;
+		*use_dict = true;
+	}
+	return st;
+}
+
 // ---- BGZF: one member with the "BC" subfield at p (left bytes from there on) -------------------------------------
 // Its total size (BSIZE + 1), or 0.  The checks of the host's scanner (nxz_blocked.cpp member_size): FLG = FEXTRA
 // alone, XLEN >= 6, the subfield anywhere among the others, the size covers header and trailer and lies inside `left`.

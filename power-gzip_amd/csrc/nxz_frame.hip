@@ -53,15 +53,19 @@ __device__ inline uint32_t trailer_bytes(uint32_t format) { return format == NXZ
 
 // four wavefronts a workgroup, a job each (every lane runs the parser on the same bytes: the name / comment scans and
 // the header CRC are the steps that use them all)
-__global__ __launch_bounds__(256) void frame_header_kernel(int fmt, const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
-							   nxz_batch_frame_t *__restrict__ frames, nxz_batch_job_t *__restrict__ derived)
+// (DICT, nxz_batch_decompress_framed_dict: the caller holds a preset dictionary of that DICTID.  The derived job of a zlib
+// stream that names it is decoded with the dictionary; every other job's says NXZ_JOB_NO_DICT.)
+template <bool DICT>
+__device__ __forceinline__ void frame_header_body(int fmt, const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
+						  nxz_batch_frame_t *__restrict__ frames, nxz_batch_job_t *__restrict__ derived, uint32_t dictid)
 {
 	const uint32_t lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (i >= n) return;
 	const nxz_batch_job_t job = jobs[i];
 	nxz_batch_frame_t f;
 	WaveOps ops{lane};
-	uint32_t st = nxz_frame_parse(job.src, job.src_len, fmt, &f, ops);
+	bool use_dict = false;
+	uint32_t st = DICT ? nxz_frame_parse_dict(job.src, job.src_len, fmt, &f, ops, true, dictid, &use_dict) : nxz_frame_parse(job.src, job.src_len, fmt, &f, ops);
 	if (st == NXZ_FRAME_OK && (job.resume || job.hist_len)) st = NXZ_FRAME_BAD_HEADER;
 	if (st == NXZ_FRAME_OK && job.src_len - f.hdr_len < trailer_bytes(f.format)) st = NXZ_FRAME_TRUNCATED;
 	f.status = st;
@@ -74,7 +78,18 @@ __global__ __launch_bounds__(256) void frame_header_kernel(int fmt, const nxz_ba
 		d.src_len = job.src_len - f.hdr_len - trailer_bytes(f.format);
 		d.dst_cap = job.dst_cap;
 	}
+	if (DICT && !use_dict) d.reserved = NXZ_JOB_NO_DICT;
 	derived[i] = d;
+}
+__global__ __launch_bounds__(256) void frame_header_kernel(int fmt, const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
+							   nxz_batch_frame_t *__restrict__ frames, nxz_batch_job_t *__restrict__ derived)
+{
+	frame_header_body<false>(fmt, jobs, n, frames, derived, 0);
+}
+__global__ __launch_bounds__(256) void frame_header_dict_kernel(int fmt, const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
+								nxz_batch_frame_t *__restrict__ frames, nxz_batch_job_t *__restrict__ derived, uint32_t dictid)
+{
+	frame_header_body<true>(fmt, jobs, n, frames, derived, dictid);
 }
 
 __global__ __launch_bounds__(256) void frame_trailer_kernel(const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
@@ -307,6 +322,14 @@ extern "C" int nxz_launch_frame_header(int fmt, const nxz_batch_job_t *jobs, siz
 {
 	if (!n) return 0;
 	hipLaunchKernelGGL(nxzf::frame_header_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, fmt, jobs, (uint32_t)n, frames, derived);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames, nxz_batch_job_t *derived,
+					    uint32_t dictid, hipStream_t stream)
+{
+	if (!n) return 0;
+	hipLaunchKernelGGL(nxzf::frame_header_dict_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, fmt, jobs, (uint32_t)n, frames, derived, dictid);
 	return (int)hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include "nxz_device.h"
+#include "nxz_dict.h"
 #include "nxz_inflate_tables.h"
 
 #ifndef NXZ_INFLATE_CHAIN_BY_LANE
@@ -381,10 +382,15 @@ __device__ __forceinline__ int read_dht(Bits &b, Smem &sm, int &hlit, int &hdist
 // The target holds 16-bit elements (job.dst_cap counts elements): a byte, or 0x8000 | k for "byte k
 // of the 32 KiB that precede this output", which is what a match that reaches back before the output
 // copies; matches copy elements, so such references travel.  No history bytes are read, no checksums.
-template <bool GW, bool W16>
+// SH (with GW; nxz_batch_decompress_dict's hand-backs): the history is not in front of the job's source but ONE preset
+// dictionary for all jobs -- sh_len bytes that end at sh_end --, unless the job says NXZ_JOB_NO_DICT; job.src is the stream
+// alone, and a job that brings resume state or a history of its own is refused (NXZ_CC_INVALID_OP, nothing written).
+// Only jobs of fewer than sh_below source bytes are decoded (the launch over a whole batch for its small streams).
+template <bool GW, bool W16, bool SH = false>
 __device__ __forceinline__ void inflate_body(const nxz_batch_job_t *__restrict__ jobs,
 					     nxz_batch_result_t *__restrict__ results,
-					     nxz_batch_dht_t *__restrict__ dht_io, const Built *__restrict__ built, const uint32_t *__restrict__ order)
+					     nxz_batch_dht_t *__restrict__ dht_io, const Built *__restrict__ built, const uint32_t *__restrict__ order,
+					     const uint8_t *__restrict__ sh_end = nullptr, uint32_t sh_len = 0, uint32_t sh_below = 0xffffffffu)
 {
 	__shared__ __attribute__((aligned(16))) SmemT<GW, W16> sm;
 	typedef typename SmemT<GW, W16>::elem_t elem_t;
@@ -403,14 +409,21 @@ __device__ __forceinline__ void inflate_body(const nxz_batch_job_t *__restrict__
 	}
 	// (a piece of a stream -- W16 -- has no history in front of its source: hist_len is the bit it starts at, counted
 	// from src, which nxz_pinflate.cpp keeps 16-byte aligned inside the caller's stream)
-	const uint32_t hist_bytes = W16 ? 0 : job.hist_len < job.src_len ? job.hist_len : job.src_len;
-	const uint32_t hist = W16 ? WIN : hist_bytes;      // how far back a match may reach before the output
+	if constexpr (SH) {
+		if (sh_below != 0xffffffffu && !nxz_dict_small_stream(job.src, job.src_len, sh_below)) return;   // (the workgroup kernel's: see nxz_launch_inflate_wg_dict)
+		if (job.resume || job.hist_len) {
+			if (lane == 0) { nxz_batch_result_t r = {}; r.cc = NXZ_CC_INVALID_OP; results[jid] = r; }
+			return;
+		}
+	}
+	const uint32_t hist_bytes = W16 || SH ? 0 : job.hist_len < job.src_len ? job.hist_len : job.src_len;
+	const uint32_t hist = W16 ? WIN : SH ? ((job.reserved & NXZ_JOB_NO_DICT) ? 0 : sh_len < WIN ? sh_len : WIN) : hist_bytes;      // how far back a match may reach before the output
 	uint32_t srclen = job.src_len - hist_bytes;          // (a piece of a stream may run on behind it: `ext` below)
 	const NXZ_GLOBAL_AS uint8_t *src = (const NXZ_GLOBAL_AS uint8_t *)job.src + hist_bytes;
 	NXZ_GLOBAL_AS uint8_t *dst = (NXZ_GLOBAL_AS uint8_t *)job.dst;
 	const uint32_t cap = job.dst_cap;
 	// window access: position p counts output bytes, negative positions (as uint32) are history
-	const NXZ_GLOBAL_AS uint8_t *hist_end = (const NXZ_GLOBAL_AS uint8_t *)job.src + hist_bytes;
+	const NXZ_GLOBAL_AS uint8_t *hist_end = SH ? (const NXZ_GLOBAL_AS uint8_t *)sh_end : (const NXZ_GLOBAL_AS uint8_t *)job.src + hist_bytes;
 	NXZ_GLOBAL_AS uint16_t *dst16 = (NXZ_GLOBAL_AS uint16_t *)job.dst;
 	auto wr = [&](uint32_t p, uint32_t v) __attribute__((always_inline)) {
 		if (W16 && GW) dst16[p] = (uint16_t)v;
@@ -1090,6 +1103,13 @@ __global__ __launch_bounds__(64) void inflate_kernel<false, true>(const nxz_batc
 	inflate_body<false, true>(jobs, results, dht_io, built, order);
 }
 
+// the jobs of a batch that shares a preset dictionary (the target as window; see inflate_body, SH)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void inflate_dict_kernel(const nxz_batch_job_t *__restrict__ jobs,
+		nxz_batch_result_t *__restrict__ results, const uint32_t *__restrict__ order, const uint8_t *__restrict__ dict_end, uint32_t dlen, uint32_t src_below)
+{
+	inflate_body<true, false, true>(jobs, results, nullptr, nullptr, order, dict_end, dlen, src_below);
+}
+
 // ---- token boundaries inside a dynamic block (nxz_inflate_stream, few pieces) ----
 // A block is the unit the pieces of a stream are cut at, and a wavefront takes milliseconds for one: a
 // caller that holds a megabyte of the stream has some forty blocks, and waits for the longest.  Inside
@@ -1304,6 +1324,15 @@ extern "C" int nxz_launch_inflate_order_only(const nxz_batch_job_t *jobs, size_t
 {
 	if (!nslots) return 0;
 	hipLaunchKernelGGL(nxzi::inflate_kernel<true>, dim3((unsigned)nslots), dim3(64), 0, stream, jobs, results, dht_io, (const nxzi::Built *)nullptr, order);
+	return (int)hipGetLastError();
+}
+
+// ... of a batch whose streams share a preset dictionary: dlen bytes that end at dict_end
+extern "C" int nxz_launch_inflate_order_only_dict(const nxz_batch_job_t *jobs, size_t nslots, nxz_batch_result_t *results, const uint32_t *order,
+						  const uint8_t *dict_end, uint32_t dlen, uint32_t src_below, hipStream_t stream)
+{
+	if (!nslots) return 0;
+	hipLaunchKernelGGL(nxzi::inflate_dict_kernel, dim3((unsigned)nslots), dim3(64), 0, stream, jobs, results, order, dict_end, dlen, src_below);
 	return (int)hipGetLastError();
 }
 

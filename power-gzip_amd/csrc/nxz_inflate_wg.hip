@@ -33,10 +33,12 @@
 #include <stdlib.h>
 #include <stdint.h>
 #include "nxz_device.h"
+#include "nxz_dict.h"
 #define NXZ_WG_GLOBAL NXZ_GLOBAL_AS
 #else
 #include <stdint.h>
 #include "../../include/nxz_engine.h"
+#include "nxz_dict.h"
 #define NXZ_WG_GLOBAL
 #endif
 
@@ -990,10 +992,21 @@ NXZ_WG_PHASE void flush_out(NXZ_WG_GLOBAL uint8_t *dst, bool final, int prof)
 }
 #undef WGPROF
 
-template <bool PROF>
-__global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *__restrict__ jobs, uint32_t n, nxz_batch_result_t *__restrict__ results,
-							 const uint32_t *__restrict__ order, uint32_t *__restrict__ ctr, uint32_t *__restrict__ bail,
-							 uint32_t pmin_bits, uint32_t coop, uint32_t *__restrict__ dbg, unsigned long long *__restrict__ prof)
+// The body of the kernels below.  DICT (inflate_wg_dict_kernel, nxz_batch_decompress_dict): every stream of the batch may
+// reach into one preset dictionary.  dwin: 32 KiB of device memory whose LAST dlen bytes are the inflate window (16-byte
+// aligned; what stands in front of them is never looked at).  Before a stream's first block the workgroup copies them to
+// the end of the first half of L.out and takes the state a flush_out leaves behind -- outn = fl0 = HALF, the first byte the
+// stream makes at LDS position HALF and target position 0 (aoff + HALF == 0 mod 2^32) -- with one difference: a distance may
+// reach no further than L.lowest = HALF - dlen, which moves down with every flush like the bytes themselves.  So the
+// matches, the spans and the flushes work as for any stream that has run for a while, and the dictionary is never written
+// to the target.  A job with NXZ_JOB_NO_DICT (or dlen = 0) starts as in the plain kernel.
+// src_min: a stream costs this kernel 84 000 - 95 000 cycles whatever its size (profiles/r08_dict.txt), so streams of fewer source
+// bytes than that are not its own: it passes them by (no hand-back, no result), nxzi::inflate_dict_kernel decodes them a wavefront each.
+template <bool PROF, bool DICT>
+__device__ __forceinline__ void inflate_wg_body(const nxz_batch_job_t *__restrict__ jobs, uint32_t n, nxz_batch_result_t *__restrict__ results,
+						 const uint32_t *__restrict__ order, uint32_t *__restrict__ ctr, uint32_t *__restrict__ bail,
+						 uint32_t pmin_bits, uint32_t coop, uint32_t *__restrict__ dbg, unsigned long long *__restrict__ prof,
+						 const uint8_t *__restrict__ dwin, uint32_t dlen, uint32_t src_min)
 {
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	uint8_t *ob = (uint8_t *)L.out;
@@ -1015,6 +1028,7 @@ __global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *_
 		const uint32_t jid = L.jid;
 		if (jid == 0xffffffffu) break;
 		const nxz_batch_job_t job = jobs[jid];
+		if (DICT && nxz_dict_small_stream(job.src, job.src_len, src_min)) continue;   // (not this kernel's: see above)
 		const uint32_t off = (uint32_t)((uintptr_t)job.src & 15);
 		const uint32_t nbytes = off + job.src_len;                     // the stream's bytes from its first 16-byte granule on
 		const bool takes = job.resume == 0 && job.hist_len == 0 && job.src_len > 0 && job.src_len < (1u << 28) && ((uintptr_t)job.dst & 15) == 0;
@@ -1023,14 +1037,25 @@ __global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *_
 			if (tid == 0) { const uint32_t at = atomicAdd(bail, 1u); bail[64 + at] = jid; if (dbg) atomicAdd(&dbg[R_JOB], 1u); }
 			continue;
 		}
+		// (the dictionary's share of LDS: the first half of the output)
+		const uint32_t win = DICT && !(job.reserved & NXZ_JOB_NO_DICT) ? (dlen < HALF ? dlen : HALF) : 0;
 		// a stream that may not fit LDS in one piece goes in spans sized by what it made of its source so far
-		const bool longmode = nbytes > SRC_MAX || job.dst_cap > OUT_MAX + 40960;
+		// (with a window half of L.out is taken before the stream makes a byte: the output that still fits without spans is HALF less)
+		const bool longmode = nbytes > SRC_MAX || job.dst_cap > OUT_MAX + 40960 - (win ? HALF : 0);
 		const NXZ_WG_GLOBAL uint8_t *gsrc = (const NXZ_WG_GLOBAL uint8_t *)(job.src - off);
 		{
 			v4u *b0 = (v4u *)L.mstart;
 			const v4u z = { 0, 0, 0, 0 };
 			for (uint32_t i = tid; i < OUT_MAX / 32 / 4; i += NT) b0[i] = z;
 			if (tid == 0) L.pos = off * 8;
+		}
+		if (DICT && win) {
+			// the window, 16 bytes a lane: the granules of dwin that hold its last `win` bytes to the same place of L.out
+			const NXZ_WG_GLOBAL v4u *g = (const NXZ_WG_GLOBAL v4u *)dwin;
+			v4u *o4 = (v4u *)L.out;
+			for (uint32_t i = ((HALF - win) >> 4) + (uint32_t)tid; i < HALF / 16; i += NT) o4[i] = g[i];
+			if (tid == 0) { L.outn = HALF; L.fl0 = HALF; L.aoff = 0u - HALF; L.lowest = HALF - win; }
+			WGPROF(P_LOAD);
 		}
 		if (PROF && tid == 0) L.prof[P_STREAMS]++;
 
@@ -1043,6 +1068,7 @@ __global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *_
 				// (a flush frees 32 KiB at least: a piece that makes more than that is not this kernel's)
 				if (outn <= HALF || outn == L.fl0) { __syncthreads(); if (tid == 0) L.bail = R_SPACE; continue; }
 				flush_out((NXZ_WG_GLOBAL uint8_t *)job.dst, false, PROF);
+				if (DICT && tid == 0) { const uint32_t shift = outn - HALF, low = L.lowest; L.lowest = low > shift ? low - shift : 0; }   // (the window's bytes moved down with the rest)
 				continue;
 			}
 			uint32_t spanbits = longmode ? 24576u * 8 : 0xffffffffu;
@@ -1172,11 +1198,31 @@ __global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *_
 #undef WGPROF
 }
 
+template <bool PROF>
+__global__ __launch_bounds__(NT) void inflate_wg_kernel(const nxz_batch_job_t *__restrict__ jobs, uint32_t n, nxz_batch_result_t *__restrict__ results,
+							 const uint32_t *__restrict__ order, uint32_t *__restrict__ ctr, uint32_t *__restrict__ bail,
+							 uint32_t pmin_bits, uint32_t coop, uint32_t *__restrict__ dbg, unsigned long long *__restrict__ prof)
+{
+	inflate_wg_body<PROF, false>(jobs, n, results, order, ctr, bail, pmin_bits, coop, dbg, prof, nullptr, 0, 0);
+}
+
+// ... with one preset dictionary for all streams (see inflate_wg_body)
+template <bool PROF>
+__global__ __launch_bounds__(NT) void inflate_wg_dict_kernel(const nxz_batch_job_t *__restrict__ jobs, uint32_t n, nxz_batch_result_t *__restrict__ results,
+							      const uint32_t *__restrict__ order, uint32_t *__restrict__ ctr, uint32_t *__restrict__ bail,
+							      uint32_t pmin_bits, uint32_t coop, uint32_t *__restrict__ dbg, unsigned long long *__restrict__ prof,
+							      const uint8_t *__restrict__ dwin, uint32_t dlen, uint32_t src_min)
+{
+	inflate_wg_body<PROF, true>(jobs, n, results, order, ctr, bail, pmin_bits, coop, dbg, prof, dwin, dlen, src_min);
+}
+
 } // namespace nxzw
 
 #ifndef NXZ_CPU_SIM
 extern "C" int nxz_launch_inflate_order_only(const nxz_batch_job_t *jobs, size_t nslots, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io,
 					     const uint32_t *order, hipStream_t stream);
+extern "C" int nxz_launch_inflate_order_only_dict(const nxz_batch_job_t *jobs, size_t nslots, nxz_batch_result_t *results, const uint32_t *order,
+						  const uint8_t *dict_end, uint32_t dlen, uint32_t src_below, hipStream_t stream);
 
 // control words of a launch: the job counter, the reasons, then the hand-back list (a count, the indices from word 64 on)
 extern "C" size_t nxz_inflate_wg_workspace(size_t n)
@@ -1188,8 +1234,23 @@ extern "C" size_t nxz_inflate_wg_workspace(size_t n)
 // case, a wavefront each (nxzi::inflate_kernel through the list: a slot that holds no job ends at once).  order (may be
 // NULL): the jobs by falling source length.  Checksums by nxzl::cksum_kernel -- with targets (may be NULL), the outputs go
 // there in the same pass (the rounds of nxu_run_job: device buffers to pinned host memory).
+static int launch_inflate_wg(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io,
+			     uint8_t *wg_ws, const uint32_t *order, uint8_t *const *targets, const uint8_t *dwin, uint32_t dlen, bool with_dict, uint32_t src_min, hipStream_t stream);
 extern "C" int nxz_launch_inflate_wg(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io,
 				     uint8_t *wg_ws, const uint32_t *order, uint8_t *const *targets, hipStream_t stream)
+{
+	return launch_inflate_wg(jobs, n, results, dht_io, wg_ws, order, targets, nullptr, 0, false, 0, stream);
+}
+// The same for streams that share a preset dictionary (nxz_batch_decompress_dict): dwin = 32 KiB whose last dlen bytes are the
+// inflate window; the streams handed back go a wavefront each through the kernel that reads the window from there.
+// src_min: streams of fewer source bytes go a wavefront each from the start (one launch over all jobs in front of the workgroup kernel's).
+extern "C" int nxz_launch_inflate_wg_dict(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint8_t *wg_ws,
+					  const uint32_t *order, const uint8_t *dwin, uint32_t dlen, uint32_t src_min, hipStream_t stream)
+{
+	return launch_inflate_wg(jobs, n, results, nullptr, wg_ws, order, nullptr, dwin, dlen, true, src_min, stream);
+}
+static int launch_inflate_wg(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io,
+			     uint8_t *wg_ws, const uint32_t *order, uint8_t *const *targets, const uint8_t *dwin, uint32_t dlen, bool with_dict, uint32_t src_min, hipStream_t stream)
 {
 	if (!n) return 0;
 	if (n >= (1u << 31)) return (int)hipErrorInvalidValue;
@@ -1206,6 +1267,18 @@ extern "C" int nxz_launch_inflate_wg(const nxz_batch_job_t *jobs, size_t n, nxz_
 	const unsigned coop = nre && atoi(nre) >= 0 && atoi(nre) <= 1024 ? (unsigned)atoi(nre) : 16u;
 	const unsigned grid = (unsigned)(n < cus ? n : cus);
 	const char *pr = getenv("NXZ_WG_PROF");
+	if (with_dict) {
+		if (src_min) {
+			const int rc0 = nxz_launch_inflate_order_only_dict(jobs, n, results, nullptr, dwin + nxzw::HALF, dlen, src_min, stream);
+			if (rc0) return rc0;
+		}
+		if (pr && atoi(pr)) hipLaunchKernelGGL(nxzw::inflate_wg_dict_kernel<true>, dim3(grid), dim3(nxzw::NT), 0, stream, jobs, (uint32_t)n, results, order, ctr, bail, pmin | maxr << 16, coop, dbg, prof, dwin, dlen, src_min);
+		else hipLaunchKernelGGL(nxzw::inflate_wg_dict_kernel<false>, dim3(grid), dim3(nxzw::NT), 0, stream, jobs, (uint32_t)n, results, order, ctr, bail, pmin | maxr << 16, coop, dbg, prof, dwin, dlen, src_min);
+		int rc = (int)hipGetLastError();
+		if (rc) return rc;
+		rc = nxz_launch_inflate_order_only_dict(jobs, n, results, bail + 64, dwin + nxzw::HALF, dlen, 0xffffffffu, stream);
+		return rc ? rc : nxz_launch_cksum(jobs, n, results, stream);
+	}
 	if (pr && atoi(pr)) hipLaunchKernelGGL(nxzw::inflate_wg_kernel<true>, dim3(grid), dim3(nxzw::NT), 0, stream, jobs, (uint32_t)n, results, order, ctr, bail, pmin | maxr << 16, coop, dbg, prof);
 	else hipLaunchKernelGGL(nxzw::inflate_wg_kernel<false>, dim3(grid), dim3(nxzw::NT), 0, stream, jobs, (uint32_t)n, results, order, ctr, bail, pmin | maxr << 16, coop, dbg, prof);
 	int rc = (int)hipGetLastError();

@@ -42,6 +42,7 @@
 #include <stdint.h>
 #include "nxz_device.h"
 #include "nxz_dhtgen_dev.h"
+#include "nxz_dict.h"
 
 // Diagnostic only (tools/phase_profile.py, a build with -DNXZ_LZ77_PROF: tools/build_variant.sh prof nxz_lz77.hip -DNXZ_LZ77_PROF):
 // per-phase cycle sums of every workgroup's thread 0.  Compiled out of the product: the counters cost a dozen
@@ -605,11 +606,17 @@ __device__ __forceinline__ void post(uint8_t *lds, const nxz_batch_job_t *__rest
 }
 } // namespace gen
 
-template <bool COUNT, bool FUSED = false, bool GEN = false>
-__global__ __launch_bounds__(NT) void lz77_kernel(const nxz_batch_job_t *__restrict__ jobs,
-						  uint8_t *__restrict__ tokens, uint16_t *__restrict__ cand2,
-						  nxz_batch_result_t *__restrict__ results,
-						  uint32_t *__restrict__ counts, uint32_t njobs, uint32_t *__restrict__ next_job)
+// The body of the kernels below.  DICT (lz77_dict_kernel, nxz_batch_compress_dict): the window of every job is the same
+// `dict` -- job.hist_len bytes of it, a multiple of 16.  The jobs are nxzl77::dict_jobs_kernel's: job.src is where the window
+// WOULD stand if it lay in front of the source, so job.src + job.hist_len is the source as ever.  THE BYTES [job.src, job.src +
+// job.hist_len) ARE NOT THE CALLER'S MEMORY: with DICT nothing may read them (the load phase takes them from `dict`, the only
+// place the two forms differ).
+template <bool COUNT, bool FUSED, bool GEN, bool DICT>
+__device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jobs,
+					  uint8_t *__restrict__ tokens, uint16_t *__restrict__ cand2,
+					  nxz_batch_result_t *__restrict__ results,
+					  uint32_t *__restrict__ counts, uint32_t njobs, uint32_t *__restrict__ next_job,
+					  const uint8_t *__restrict__ dict)
 {
 	// (a static array: its address is a compile-time constant, 0; with `extern __shared__` every LDS address of the
 	// kernel carried one more vector add -- of a link-time zero --, 117 of them)
@@ -673,11 +680,18 @@ __global__ __launch_bounds__(NT) void lz77_kernel(const nxz_batch_job_t *__restr
 		const NXZ_GLOBAL v4u *s4 = (const NXZ_GLOBAL v4u *)src;
 		v4u *d4 = (v4u *)inw;
 		uint32_t nfull = total >> 4;
+		if constexpr (DICT) {
+			// the shared window (in L2 after the first workgroups), then the job's own bytes behind it: s4[i] is read from
+			// i = h / 16 on only -- below that job.src points in front of the caller's buffer
+			const NXZ_GLOBAL v4u *w4 = (const NXZ_GLOBAL v4u *)dict;
+			const uint32_t hq = h >> 4;
+			for (uint32_t i = t; i < nfull; i += NT) d4[i] = i < hq ? w4[i] : s4[i];
+		} else
 		for (uint32_t i = t; i < nfull; i += NT) d4[i] = s4[i];
 		// tail bytes + zero pad (so that over-reads past `end` are defined)
 		uint32_t base = nfull << 4;
 		for (uint32_t i = base + t; i < base + 48 && i < 65536 + 32; i += NT)
-			lds[OFF_IN + i] = i < total ? src[i] : 0;
+			lds[OFF_IN + i] = i < total ? src[i] : 0;                      // (DICT: behind the window, a multiple of 16 bytes)
 	}
 	for (uint32_t i = t; i < HSIZE; i += NT) head[i] = 0;
 	if (t < 316) hist[t] = 0;
@@ -1842,7 +1856,7 @@ __global__ __launch_bounds__(NT) void lz77_kernel(const nxz_batch_job_t *__restr
 	if (t == 0) {
 		nxz_batch_result_t r;
 		r.cc = 0; r.tpbc = 0; r.tebc = 0;
-		r.spbc = total; r.crc = out_crc; r.adler = out_adler; r.subc = 0;
+		r.spbc = DICT ? n : total; r.crc = out_crc; r.adler = out_adler; r.subc = 0;
 		r.sfbt = misc[M_NREC];                                  // match tokens (diagnostic; the entropy stage checks it against the record array's size)
 		if constexpr (FUSED) {
 			// end of block (seven zero bits) behind what the tiles left, the last bytes, the completion code
@@ -1896,7 +1910,67 @@ __global__ __launch_bounds__(NT) void lz77_kernel(const nxz_batch_job_t *__restr
 	}
 }
 
+template <bool COUNT, bool FUSED = false, bool GEN = false>
+__global__ __launch_bounds__(NT) void lz77_kernel(const nxz_batch_job_t *__restrict__ jobs,
+						  uint8_t *__restrict__ tokens, uint16_t *__restrict__ cand2,
+						  nxz_batch_result_t *__restrict__ results,
+						  uint32_t *__restrict__ counts, uint32_t njobs, uint32_t *__restrict__ next_job)
+{
+	lz77_body<COUNT, FUSED, GEN, false>(jobs, tokens, cand2, results, counts, njobs, next_job, nullptr);
+}
+
+// ... with one window for all jobs (nxz_batch_compress_dict)
+template <bool COUNT, bool FUSED = false, bool GEN = false>
+__global__ __launch_bounds__(NT) void lz77_dict_kernel(const nxz_batch_job_t *__restrict__ jobs,
+						       uint8_t *__restrict__ tokens, uint16_t *__restrict__ cand2,
+						       nxz_batch_result_t *__restrict__ results,
+						       uint32_t *__restrict__ counts, uint32_t njobs, uint32_t *__restrict__ next_job,
+						       const uint8_t *__restrict__ dict)
+{
+	lz77_body<COUNT, FUSED, GEN, true>(jobs, tokens, cand2, results, counts, njobs, next_job, dict);
+}
+
+// The caller's jobs (source alone, no history) as the kernels see them: the window of W bytes in front -- src_len and hist_len
+// say so, src points to where the window would begin.  Nothing reads below the source itself: lz77_dict_kernel takes the first
+// hist_len bytes from the dictionary, the entropy kernel (nxz_encode.hip: `src + h`) reads [src + hist_len, src + src_len) and a
+// kernel that ever needs the history itself must take it from the dictionary for these jobs.  A job the
+// dictionary calls do not take (a history of its own, window + source beyond the 64 KiB block) becomes an empty job with no
+// room, which every kernel ends without a store to its target; dict_finish_kernel then writes its result.
+__global__ __launch_bounds__(256) void dict_jobs_kernel(const nxz_batch_job_t *__restrict__ in, uint32_t n, uint32_t W, nxz_batch_job_t *__restrict__ out)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	nxz_batch_job_t j = in[i];
+	if (nxz_dict_job_fits(W, j.src_len, j.hist_len)) {
+		j.src = (const uint8_t *)((uintptr_t)j.src - W);
+		j.src_len += W; j.hist_len = W;
+	} else { j.src_len = 0; j.hist_len = 0; j.dst_cap = 0; }
+	out[i] = j;
+}
+__global__ __launch_bounds__(256) void dict_finish_kernel(const nxz_batch_job_t *__restrict__ in, uint32_t n, uint32_t W, nxz_batch_result_t *__restrict__ results)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	if (nxz_dict_job_fits(W, in[i].src_len, in[i].hist_len)) return;
+	nxz_batch_result_t r = {};
+	r.cc = NXZ_CC_INVALID_OP;
+	results[i] = r;
+}
+
 } // namespace nxzl77
+
+extern "C" int nxz_launch_dict_jobs(const nxz_batch_job_t *in, size_t n, uint32_t W, nxz_batch_job_t *out, hipStream_t stream)
+{
+	if (!n) return 0;
+	hipLaunchKernelGGL(nxzl77::dict_jobs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (uint32_t)n, W, out);
+	return (int)hipGetLastError();
+}
+extern "C" int nxz_launch_dict_finish(const nxz_batch_job_t *in, size_t n, uint32_t W, nxz_batch_result_t *results, hipStream_t stream)
+{
+	if (!n) return 0;
+	hipLaunchKernelGGL(nxzl77::dict_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, (uint32_t)n, W, results);
+	return (int)hipGetLastError();
+}
 
 extern "C" int nxz_lz77_prof_set(unsigned long long *buf)
 {
@@ -1913,8 +1987,21 @@ extern "C" int nxz_lz77_prof_set(unsigned long long *buf)
 extern "C" size_t nxz_lz77_gen_scratch_bytes(void) { return nxzl77::gen::table_off(NXZ_LZ77_MAX_GRID) + (size_t)NXZ_LZ77_MAX_GRID * 2 * sizeof(nxz_dht_prepared_t); }
 extern "C" size_t nxz_lz77_cand2_bytes(void) { return (size_t)NXZ_LZ77_MAX_GRID * nxzl77::C2_STRIDE * sizeof(uint16_t); }
 
+static int launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
+		       uint32_t *counts, uint32_t *job_counter, const uint8_t *dict, bool with_dict, hipStream_t stream);
 extern "C" int nxz_launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
 			       uint32_t *counts, uint32_t *job_counter, hipStream_t stream)
+{
+	return launch_lz77(count, jobs, n, tokens, cand2, results, counts, job_counter, nullptr, false, stream);
+}
+// the same with one window for all jobs: `jobs` as nxz_launch_dict_jobs writes them, dict = the deflate window (16-byte aligned)
+extern "C" int nxz_launch_lz77_dict(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
+				    uint32_t *counts, uint32_t *job_counter, const uint8_t *dict, hipStream_t stream)
+{
+	return launch_lz77(count, jobs, n, tokens, cand2, results, counts, job_counter, dict, true, stream);
+}
+static int launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
+		       uint32_t *counts, uint32_t *job_counter, const uint8_t *dict, bool with_dict, hipStream_t stream)
 {
 	using namespace nxzl77;
 	if (n == 0) return 0;
@@ -1937,6 +2024,12 @@ extern "C" int nxz_launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n,
 	const unsigned grid = (unsigned)(n < (size_t)ncu ? n : (size_t)ncu);
 	if (n <= grid) job_counter = nullptr;                      // one job per workgroup: nothing to draw
 	if (job_counter && hipMemsetAsync(job_counter, 0, sizeof(uint32_t), stream) != hipSuccess) job_counter = nullptr;
+	if (with_dict) {
+		void (*kd)(const nxz_batch_job_t *, uint8_t *, uint16_t *, nxz_batch_result_t *, uint32_t *, uint32_t, uint32_t *, const uint8_t *);
+		kd = count == 3 ? lz77_dict_kernel<true, false, true> : count == 2 ? lz77_dict_kernel<false, true> : count ? lz77_dict_kernel<true> : lz77_dict_kernel<false>;
+		hipLaunchKernelGGL(kd, dim3(grid), dim3(NT), 0, stream, jobs, tokens, cand2, results, counts, (uint32_t)n, job_counter, dict);
+		return (int)hipGetLastError();
+	}
 	hipLaunchKernelGGL(k, dim3(grid), dim3(NT), 0, stream, jobs, tokens, cand2, results, counts, (uint32_t)n, job_counter);
 	return (int)hipGetLastError();
 }

@@ -330,20 +330,23 @@ __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t
 // big-endian.  Offsets as member_offsets_kernel, with the zlib overhead.
 #define NXZ_ZLIB_OVERHEAD 6u         /* CMF FLG + Adler-32 */
 
-__device__ inline uint32_t zlib_member_size(const nxz_batch_job_t &job, const nxz_batch_result_t &r)
+__device__ inline uint32_t zlib_member_size(const nxz_batch_job_t &job, const nxz_batch_result_t &r, uint32_t extra = 0)
 {
-	return NXZ_ZLIB_OVERHEAD + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
+	return NXZ_ZLIB_OVERHEAD + extra + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
 }
 
-__global__ __launch_bounds__(1024) void zlib_offsets_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
-							    uint32_t n, uint64_t *__restrict__ offsets)
+// (FDICT: the streams name a preset dictionary -- four bytes of DICTID behind FLG, nxz_batch_pack_zlib_dict)
+template <bool FDICT>
+__device__ __forceinline__ void zlib_offsets_body(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+						  uint32_t n, uint64_t *__restrict__ offsets)
 {
+	constexpr uint32_t X = FDICT ? 4 : 0;
 	__shared__ uint64_t part[1024];
 	const uint32_t t = threadIdx.x;
 	const uint32_t per = (n + 1023) / 1024;
 	const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
 	uint64_t sum = 0;
-	for (uint32_t i = lo; i < hi; i++) sum += zlib_member_size(jobs[i], results[i]);
+	for (uint32_t i = lo; i < hi; i++) sum += zlib_member_size(jobs[i], results[i], X);
 	part[t] = sum;
 	__syncthreads();
 	for (uint32_t d = 1; d < 1024; d <<= 1) {
@@ -355,29 +358,42 @@ __global__ __launch_bounds__(1024) void zlib_offsets_kernel(const nxz_batch_job_
 	uint64_t off = part[t] - sum;
 	for (uint32_t i = lo; i < hi; i++) {
 		offsets[i] = off;
-		off += zlib_member_size(jobs[i], results[i]);
+		off += zlib_member_size(jobs[i], results[i], X);
 	}
 	if (t == 1023) offsets[n] = part[1023];
 }
+__global__ __launch_bounds__(1024) void zlib_offsets_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+							    uint32_t n, uint64_t *__restrict__ offsets)
+{
+	zlib_offsets_body<false>(jobs, results, n, offsets);
+}
+__global__ __launch_bounds__(1024) void zlib_dict_offsets_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+								 uint32_t n, uint64_t *__restrict__ offsets)
+{
+	zlib_offsets_body<true>(jobs, results, n, offsets);
+}
 
 // one workgroup per stream, written as pack_members_kernel writes a gzip member
-__global__ __launch_bounds__(256) void pack_zlib_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
-							const uint64_t *__restrict__ offsets, uint32_t flg, uint8_t *__restrict__ packed)
+template <bool FDICT>
+__device__ __forceinline__ void pack_zlib_body(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+					       const uint64_t *__restrict__ offsets, uint32_t flg, uint32_t dictid, uint8_t *__restrict__ packed)
 {
+	constexpr uint32_t X = FDICT ? 4 : 0;
 	const uint32_t t = threadIdx.x;
 	const nxz_batch_job_t job = jobs[blockIdx.x];
 	const nxz_batch_result_t r = results[blockIdx.x];
 	const uint64_t off = offsets[blockIdx.x];
 	const uint32_t len = job.src_len - job.hist_len;
 	const bool stored = member_stored(job, r);
-	const uint32_t size = zlib_member_size(job, r);
-	const uint32_t d0 = stored ? 7 : 2;                           // first byte that comes from `data`
+	const uint32_t size = zlib_member_size(job, r, X);
+	const uint32_t d0 = (stored ? 7 : 2) + X;                     // first byte that comes from `data`
 	const uint32_t dn = stored ? len : r.tpbc;
 	const uint8_t *data = stored ? job.src + job.hist_len : job.dst;
 	auto byte_at = [&](uint32_t j) -> uint32_t {
 		if (j < 2) return j == 0 ? 0x78u : flg;                 // CM 8, CINFO 7 (a 32 KiB window)
+		if (FDICT && j < 6) return (dictid >> (8 * (5 - j))) & 0xff;   // DICTID, most significant byte first
 		if (j < d0) {                                           // stored block: BFINAL=1 BTYPE=00, LEN, NLEN
-			const uint32_t k = j - 2;
+			const uint32_t k = j - 2 - X;
 			return k == 0 ? 1 : k < 3 ? (len >> (8 * (k - 1))) & 0xff : (~len >> (8 * (k - 3))) & 0xff;
 		}
 		if (j < d0 + dn) return data[j - d0];
@@ -403,6 +419,17 @@ __global__ __launch_bounds__(256) void pack_zlib_kernel(const nxz_batch_job_t *_
 		}
 		od[w] = v;
 	}
+}
+
+__global__ __launch_bounds__(256) void pack_zlib_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+							const uint64_t *__restrict__ offsets, uint32_t flg, uint8_t *__restrict__ packed)
+{
+	pack_zlib_body<false>(jobs, results, offsets, flg, 0, packed);
+}
+__global__ __launch_bounds__(256) void pack_zlib_dict_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+							     const uint64_t *__restrict__ offsets, uint32_t flg, uint32_t dictid, uint8_t *__restrict__ packed)
+{
+	pack_zlib_body<true>(jobs, results, offsets, flg, dictid, packed);
 }
 
 // ---- one deflate stream from a compress batch ---------------------------------------------------
@@ -629,6 +656,15 @@ extern "C" int nxz_launch_pack_zlib(const nxz_batch_job_t *jobs, const nxz_batch
 	if (!n) return 0;
 	hipLaunchKernelGGL(nxz::zlib_offsets_kernel, dim3(1), dim3(1024), 0, stream, jobs, results, (uint32_t)n, offsets);
 	hipLaunchKernelGGL(nxz::pack_zlib_kernel, dim3((unsigned)n), dim3(256), 0, stream, jobs, results, offsets, flg, packed);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_pack_zlib_dict(const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n, uint32_t flg, uint32_t dictid,
+					 uint64_t *offsets, uint8_t *packed, hipStream_t stream)
+{
+	if (!n) return 0;
+	hipLaunchKernelGGL(nxz::zlib_dict_offsets_kernel, dim3(1), dim3(1024), 0, stream, jobs, results, (uint32_t)n, offsets);
+	hipLaunchKernelGGL(nxz::pack_zlib_dict_kernel, dim3((unsigned)n), dim3(256), 0, stream, jobs, results, offsets, flg, dictid, packed);
 	return (int)hipGetLastError();
 }
 

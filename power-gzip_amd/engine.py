@@ -47,6 +47,40 @@ RANGE_UOFF, RANGE_VOFF = 0, 1
 RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED = range(4)
 
 
+# jobs[].reserved (include/nxz_engine.h)
+JOB_SUSPEND_WHEN_FULL, JOB_NO_DICT = 1, 2
+DICT_WINDOW = 32768
+
+
+def dict_inflate_window(n):
+    """bytes of an n-byte dictionary the decompress calls use: its last min(n, 32768)"""
+    return min(n, DICT_WINDOW)
+
+
+def dict_deflate_window(n):
+    """... and the compress calls: its last min(n, 32768) & ~15 (a compress job then carries 65536 - that many bytes at most)"""
+    return min(n, DICT_WINDOW) & ~15
+
+
+class Dict:
+    """nxz_dict_t: a preset dictionary on the device, shared by all jobs of the *_dict calls (Engine.dict_create)"""
+
+    def __init__(self, eng, data):
+        self.eng = eng
+        self.length = len(data)
+        h = C.c_void_p()
+        eng._check(eng.L.nxz_dict_create(eng.ctx, bytes(data), len(data), C.byref(h)), "nxz_dict_create")
+        self.handle = h
+        self.id = eng.L.nxz_dict_id(h)
+        self.inflate_window = dict_inflate_window(len(data))
+        self.deflate_window = dict_deflate_window(len(data))
+
+    def close(self):
+        if self.handle:
+            self.eng.L.nxz_dict_destroy(self.eng.ctx, self.handle)
+            self.handle = None
+
+
 class StreamResume(C.Structure):
     """nxz_stream_resume_t (include/nxz_engine.h): where a deflate stream stands between two calls"""
     _fields_ = [("sfbt", C.c_uint32), ("rem", C.c_uint32), ("dhtlen", C.c_uint32), ("final", C.c_uint32), ("dht", C.c_uint8 * 288)]
@@ -90,6 +124,18 @@ def load_library():
         L.nxz_batch_pack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_pack_zlib.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_decompress_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        # one preset dictionary for all jobs of a batch
+        L.nxz_dict_create.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)]
+        L.nxz_dict_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.nxz_dict_id.restype = C.c_uint32
+        L.nxz_dict_id.argtypes = [C.c_void_p]
+        L.nxz_batch_compress_dict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_decompress_dict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_batch_pack_zlib_dict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                               C.c_void_p]
+        L.nxz_batch_decompress_framed_dict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -214,6 +260,55 @@ class Engine:
         rc = self.L.nxz_batch_decompress_framed(self.ctx, fmt, jobs.data_ptr(), n, results.data_ptr(), frames.data_ptr(),
                                                 self.stream_handle())
         self._check(rc, "nxz_batch_decompress_framed")
+        return results, frames
+
+    # ---- one preset dictionary for all jobs (zlib's deflateSetDictionary / inflateSetDictionary) ----
+    def dict_create(self, data):
+        """bytes -> Dict (nxz_dict_create); close() it when no call that uses it is still running"""
+        return Dict(self, data)
+
+    def compress_dict(self, fc, d, jobs, n, results=None, dht=None, ntables=0, counts=None):
+        """nxz_batch_compress_dict: jobs[].src is the source alone, the dictionary's deflate window is every job's history"""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if (fc & 0x4) and counts is None:
+            counts = t.empty(n * 316, dtype=t.int32, device=self.dev)
+        rc = self.L.nxz_batch_compress_dict(self.ctx, fc, d.handle, jobs.data_ptr(), n,
+                                            dht.data_ptr() if dht is not None else None, ntables,
+                                            results.data_ptr(), counts.data_ptr() if counts is not None else None,
+                                            self.stream_handle())
+        self._check(rc, "nxz_batch_compress_dict")
+        return results, counts
+
+    def decompress_dict(self, d, jobs, n, results=None):
+        """nxz_batch_decompress_dict: raw deflate streams that may refer to the dictionary's inflate window"""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        self._check(self.L.nxz_batch_decompress_dict(self.ctx, d.handle, jobs.data_ptr(), n, results.data_ptr(), self.stream_handle()),
+                    "nxz_batch_decompress_dict")
+        return results
+
+    def pack_zlib_dict(self, level, d, jobs, results, n, packed, offsets=None):
+        """zlib streams with FDICT / DICTID from a compress_dict batch, nxz_batch_pack_zlib_dict.  Returns the offsets."""
+        t = self.torch
+        if offsets is None:
+            offsets = t.empty(n + 1, dtype=t.int64, device=self.dev)
+        self._check(self.L.nxz_batch_pack_zlib_dict(self.ctx, level, d.handle, jobs.data_ptr(), results.data_ptr(), n, offsets.data_ptr(),
+                                                    packed.data_ptr(), self.stream_handle()), "nxz_batch_pack_zlib_dict")
+        return offsets
+
+    def decompress_framed_dict(self, fmt, d, jobs, n, results=None, frames=None):
+        """nxz_batch_decompress_framed_dict: as decompress_framed; zlib streams that name the dictionary are decoded with it"""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if frames is None:
+            frames = t.empty(n * FRAME_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_decompress_framed_dict(self.ctx, fmt, d.handle, jobs.data_ptr(), n, results.data_ptr(), frames.data_ptr(),
+                                                     self.stream_handle())
+        self._check(rc, "nxz_batch_decompress_framed_dict")
         return results, frames
 
     def frames_to_host(self, frames):
