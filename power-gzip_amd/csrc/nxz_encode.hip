@@ -7,13 +7,15 @@
 // kernel turns them into one deflate block -- fixed code, a caller's dynamic table, or the
 // table the device built from this very job's symbol counts (nxz_dhtgen.hip).
 //
-// Position parallel: a 256-thread workgroup per job walks the block in rounds of 4096
-// positions, 16 consecutive positions per lane.  A lane knows its tokens from the two bitmaps,
+// Position parallel: a 256-thread workgroup per job walks the block in rounds of 2048
+// positions, 8 consecutive positions per lane.  A lane knows its tokens from the two bitmaps,
 // reads its literals from the source and its matches from the record array (rank of a match =
 // number of match bits in front of it; the ranks of all 2048 bitmap words are made once per job),
 // sums the code lengths, gets a bit offset from the workgroup prefix sum and ORs its codes into
-// an LDS window that leaves as coalesced dwords.  Nothing here is serial over the block, and
-// with ~15 KiB of LDS eight workgroups share a CU, so the latencies of one hide behind the others.
+// an LDS window that leaves as coalesced dwords.  A round's match records are turned into their
+// codes once each, a round ahead, by the lanes that copy them to LDS; the lanes of the round only
+// load a finished code.  Nothing here is serial over the block, and with ~21 KiB of LDS seven
+// workgroups share a CU, so the latencies of one hide behind the others.
 // Bit for bit the encoder of oracle/nxz_lz77.c (put_tokens / nxo_encode_fixed / nxo_encode_dynamic).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,63 +38,60 @@ typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 // the first position and one at the fourth).  Straight-line code, the same for every lane.
 struct Quad { uint32_t a0, a1, a2, nb; };
 
+// A match record (length - 3, distance - 1) as its finished code: x = bits 0..31, y = bits 32..47 | bit length << 16
+// (<= 20 bits of length code and extra bits, then <= 28 of distance code and extra bits).  Done once per record, by the
+// lane that copies it to LDS, not by every lane whose quad might hold a match.
 // CHECK: a symbol without a code can occur (a caller's table; the table the device made of this very block's counts has
 // a code for every symbol the block uses -- nxz_dhtgen.hip as lib/nx_dhtgen.c:252-270 -- and the fixed code for all)
 template <bool CHECK>
-__device__ __forceinline__ Quad encode_quad(const uint32_t *lltab, const uint32_t *dtab, const uint32_t *rec, uint32_t &ri,
+__device__ __forceinline__ v2u code_record(const uint32_t *lltab, const uint32_t *dtab, uint32_t r, bool &missing)
+{
+	const uint32_t l3 = r & 0xff, d = (r >> 8) & 0x7fff;
+	uint32_t le = l3 < 8 ? 0 : (29 - (uint32_t)__builtin_clz(l3 | 8));
+	const uint32_t ls = l3 == 255 ? 28 : (le << 2) + (l3 >> le);
+	if (l3 == 255) le = 0;
+	const uint32_t de = d < 4 ? 0 : (30 - (uint32_t)__builtin_clz(d | 4));
+	const uint32_t ds = d < 4 ? d : 2 * de + 2 + ((d >> de) & 1);
+	const uint32_t lt = lltab[257 + ls], dt = dtab[ds];
+	const uint32_t ll = lt >> 16, dl = dt >> 16;
+	if (CHECK) missing = ll == 0 || dl == 0;
+	const uint32_t lo = (lt & 0xffff) | ((l3 & ((1u << le) - 1)) << ll);          // <= 20 bits
+	const uint32_t hi = (dt & 0xffff) | ((d & ((1u << de) - 1)) << dl);           // <= 28 bits
+	const uint64_t mv = (uint64_t)lo | ((uint64_t)hi << (ll + le));
+	return (v2u){ (uint32_t)mv, (uint32_t)(mv >> 32) | ((ll + le + dl + de) << 16) };
+}
+
+template <bool CHECK>
+__device__ __forceinline__ Quad encode_quad(const uint32_t *lltab, const v2u *rec, uint32_t &ri,
 					    uint32_t b, uint32_t lit4, uint32_t tok4, bool &missing)
 {
-	// literals: four look-ups whether or not a literal starts there (a covered position adds no bits)
-	const uint32_t e0 = lltab[b & 0xff], e1 = lltab[(b >> 8) & 0xff], e2 = lltab[(b >> 16) & 0xff], e3 = lltab[b >> 24];
-	uint64_t v[4] = { e0 & 0xffff, e1 & 0xffff, e2 & 0xffff, e3 & 0xffff };
-	uint32_t nbk[4] = { (lit4 & 1) ? e0 >> 16 : 0, (lit4 & 2) ? e1 >> 16 : 0, (lit4 & 4) ? e2 >> 16 : 0, (lit4 & 8) ? e3 >> 16 : 0 };
+	// literals: four look-ups whether or not a literal starts there (a position without one adds no bits)
+	uint32_t e0 = lltab[b & 0xff], e1 = lltab[(b >> 8) & 0xff], e2 = lltab[(b >> 16) & 0xff], e3 = lltab[b >> 24];
 	if (CHECK) missing |= ((lit4 & 1) && !(e0 >> 16)) || ((lit4 & 2) && !(e1 >> 16)) || ((lit4 & 4) && !(e2 >> 16)) || ((lit4 & 8) && !(e3 >> 16));
-	// matches: at most two start in four positions (they are at least three bytes long), the second
-	// one only at the fourth position behind one at the first
+	e0 = (lit4 & 1) ? e0 : 0; e1 = (lit4 & 2) ? e1 : 0; e2 = (lit4 & 4) ? e2 : 0; e3 = (lit4 & 8) ? e3 : 0;
+	// the literals among themselves, <= 60 bits: two pairs in 32 bits each, one wide shift
+	const uint32_t n0 = e0 >> 16, n2 = e2 >> 16, n01 = n0 + (e1 >> 16);
+	const uint32_t p01 = (e0 & 0xffff) | ((e1 & 0xffff) << n0), p23 = (e2 & 0xffff) | ((e3 & 0xffff) << n2);
+	// the quad is x, then y: a match lies behind all its literals, but for one at the first position, where a literal
+	// (or a second match) can only follow at the fourth -- matches are at least three bytes long
+	uint64_t x = (uint64_t)p01 | ((uint64_t)p23 << n01), y = 0;
+	uint32_t nx = n01 + n2 + (e3 >> 16), ny = 0;
 	if (__ballot(tok4 != 0)) {
-		auto one = [&](uint32_t r, uint64_t &mv, uint32_t &mn) {
-			const uint32_t l3 = r & 0xff, d = (r >> 8) & 0x7fff;
-			uint32_t le = l3 < 8 ? 0 : (29 - (uint32_t)__builtin_clz(l3 | 8));
-			const uint32_t ls = l3 == 255 ? 28 : (le << 2) + (l3 >> le);
-			if (l3 == 255) le = 0;
-			const uint32_t de = d < 4 ? 0 : (30 - (uint32_t)__builtin_clz(d | 4));
-			const uint32_t ds = d < 4 ? d : 2 * de + 2 + ((d >> de) & 1);
-			const uint32_t lt = lltab[257 + ls], dt = dtab[ds];
-			const uint32_t ll = lt >> 16, dl = dt >> 16;
-			if (CHECK) missing |= ll == 0 || dl == 0;
-			const uint32_t lo = (lt & 0xffff) | ((l3 & ((1u << le) - 1)) << ll);          // <= 20 bits
-			const uint32_t hi = (dt & 0xffff) | ((d & ((1u << de) - 1)) << dl);           // <= 28 bits
-			mv = (uint64_t)lo | ((uint64_t)hi << (ll + le));
-			mn = ll + le + dl + de;
-		};
-		const uint32_t k1 = (uint32_t)__builtin_ctz(tok4 | 16);                  // 4 = none
-		uint64_t mv; uint32_t mn;
-		const bool miss0 = missing;
-		one(rec[ri], mv, mn);
-		if (!tok4) missing = miss0;
+		const v2u m = rec[ri];                                                  // coded when it was staged
+		const uint64_t mv = (uint64_t)m.x | ((uint64_t)(m.y & 0xffff) << 32);
+		const uint32_t mn = m.y >> 16;
+		if (tok4 & 1) { y = x; ny = nx; x = mv; nx = mn; }                     // (here x was the fourth position's literal alone)
+		else if (tok4) { y = mv; ny = mn; }
 		ri += tok4 ? 1 : 0;
-#pragma unroll
-		for (int k = 0; k < 4; k++) if (k1 == (uint32_t)k) { v[k] = mv; nbk[k] = mn; }
 		if (__ballot(tok4 == 9)) {
-			const bool miss1 = missing;
-			one(rec[ri], mv, mn);
-			if (tok4 != 9) missing = miss1;
-			else { v[3] = mv; nbk[3] = mn; ri++; }
+			const v2u m2 = rec[ri];
+			if (tok4 == 9) { y = (uint64_t)m2.x | ((uint64_t)(m2.y & 0xffff) << 32); ny = m2.y >> 16; ri++; }
 		}
 	}
-	// one string: token k at the sum of the lengths before it
-	uint64_t lo = nbk[0] ? v[0] : 0, hi = 0;
-	uint32_t off = nbk[0];
-#pragma unroll
-	for (int k = 1; k < 4; k++) {
-		const uint64_t x = nbk[k] ? v[k] : 0;
-		// off <= 48 + 45 here, x < 2^48
-		if (off < 64) { lo |= x << off; hi |= off ? x >> (64 - off) : 0; }
-		else hi |= x << (off - 64);
-		off += nbk[k];
-	}
+	// nx <= 60 (four literals) and y < 2^48; behind a match (nx <= 48) y is one literal or a match
+	const uint64_t lo = x | (y << nx);
 	Quad q;
-	q.a0 = (uint32_t)lo; q.a1 = (uint32_t)(lo >> 32); q.a2 = (uint32_t)hi; q.nb = off;
+	q.a0 = (uint32_t)lo; q.a1 = (uint32_t)(lo >> 32); q.a2 = nx ? (uint32_t)(y >> (64 - nx)) : 0; q.nb = nx + ny;
 	return q;
 }
 
@@ -101,11 +100,11 @@ __device__ __forceinline__ void emit_quad(uint32_t *w, const Quad &q, uint32_t b
 {
 	if (!q.nb) return;
 	const uint32_t sh = bitpos & 31, wi = bitpos >> 5, endw = (sh + q.nb + 31) >> 5;   // dwords touched: 1..4
-	const uint64_t s0 = (uint64_t)q.a0 << sh, s1 = (uint64_t)q.a1 << sh, s2 = (uint64_t)q.a2 << sh;
-	atomicOr(&w[wi], (uint32_t)s0);
-	if (endw > 1) atomicOr(&w[wi + 1], (uint32_t)(s0 >> 32) | (uint32_t)s1);
-	if (endw > 2) atomicOr(&w[wi + 2], (uint32_t)(s1 >> 32) | (uint32_t)s2);
-	if (endw > 3) atomicOr(&w[wi + 3], (uint32_t)(s2 >> 32));
+	const uint64_t s01 = (((uint64_t)q.a1 << 32) | q.a0) << sh, s12 = (((uint64_t)q.a2 << 32) | q.a1) << sh;
+	atomicOr(&w[wi], (uint32_t)s01);
+	if (endw > 1) atomicOr(&w[wi + 1], (uint32_t)(s01 >> 32));
+	if (endw > 2) atomicOr(&w[wi + 2], (uint32_t)(s12 >> 32));
+	if (endw > 3) atomicOr(&w[wi + 3], (uint32_t)(((uint64_t)q.a2 << sh) >> 32));
 }
 
 template <bool DHT, bool CHECK = DHT>
@@ -116,7 +115,9 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 	__shared__ uint32_t lltab[288];
 	__shared__ uint32_t dtab[32];
 	__shared__ __attribute__((aligned(16))) uint32_t win[2][WWORDS + 2];   // two windows: one fills while the other leaves
-	__shared__ uint32_t recbuf[2][RECMAX + 2];                             // the match records of this round and of the next
+	// the round's match tokens as finished codes (code_record).  One buffer: a round reads it before its first barrier,
+	// the next round's are written between that barrier and the second
+	__shared__ __attribute__((aligned(8))) v2u recbuf[RECMAX + 2];
 	__shared__ uint16_t rankpre[2048 + 2];                                 // matches in front of every 32 positions; [2048] = all
 	__shared__ uint32_t wsum[2][NT / 64];
 	__shared__ uint32_t errflag;
@@ -140,8 +141,8 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 
 	// What a lane needs of a round is asked for a round ahead, so that the loads' latency hides
 	// behind the work on the round before: its 8 source bytes, the two bitmap words that hold its
-	// 8 positions, and its share of the round's match records (for the LDS copy).
-	struct Fetch { v2u bytes; uint32_t litw, tokw, rec[3]; };
+	// 8 positions, and its share of the round's match records (to be coded into the LDS copy).
+	struct Fetch { v2u bytes; uint32_t litw, tokw, rec[3], nrec; };
 	auto fetch = [&](uint32_t r0, Fetch &f) {
 		const uint32_t p0 = r0 + 8 * t;
 		f.bytes = (v2u){ 0, 0 }; f.litw = 0; f.tokw = 0;
@@ -158,9 +159,27 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 		}
 	};
 	auto fetch_recs = [&](uint32_t r0, Fetch &f) {                // needs rankpre
-		const uint32_t ra = rankpre[r0 >> 5], rb = rankpre[(r0 + RPOS) >> 5 < 2048 ? (r0 + RPOS) >> 5 : 2048];
+		const uint32_t ra = __builtin_amdgcn_readfirstlane(rankpre[r0 >> 5]);
+		const uint32_t rb = __builtin_amdgcn_readfirstlane(rankpre[(r0 + RPOS) >> 5 < 2048 ? (r0 + RPOS) >> 5 : 2048]);
+		f.nrec = rb - ra < RECMAX ? rb - ra : RECMAX;
 #pragma unroll
-		for (int j = 0; j < 3; j++) f.rec[j] = ra + t + 256 * j < rb ? recs[ra + t + 256 * j] : 0;
+		for (int j = 0; j < 3; j++) f.rec[j] = t + 256 * j < f.nrec ? recs[ra + t + 256 * j] : 0;
+	};
+	bool missing = false;
+	// Every record is coded once, here, by the lane that fetched it; a pass none of the wavefront's lanes has a record
+	// for is skipped (a usual round: one pass on the first few wavefronts).  Every staged record is a token of the block.
+	auto stage_recs = [&](const Fetch &f) {
+#pragma unroll
+		for (int j = 0; j < 3; j++) {
+			const bool have = t + 256 * j < f.nrec;
+			if (!__ballot(have)) break;
+			bool miss = false;
+			const v2u c = code_record<CHECK>(lltab, dtab, f.rec[j], miss);
+			if (have) {
+				recbuf[t + 256 * j] = c;
+				if (CHECK) missing |= miss;
+			}
+		}
 	};
 	Fetch nx;
 	fetch(0, nx);                                                // round 0's bytes travel while the tables are set up
@@ -223,13 +242,11 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 	// round 0's records: no round in front to hide behind
 	{
 		fetch_recs(0, nx);
-#pragma unroll
-		for (int j = 0; j < 3; j++) if (t + 256 * j < RECMAX) recbuf[0][t + 256 * j] = nx.rec[j];
+		stage_recs(nx);
 	}
 	__syncthreads();
 
 	uint32_t wordbase = 0, par = 0;
-	bool missing = false;
 	for (uint32_t r0 = 0; r0 < n; r0 += RPOS, par ^= 1) {
 		const Fetch k = nx;
 		const bool more = r0 + RPOS < n;
@@ -243,8 +260,8 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 			// my first record: matches of the round in front of my positions
 			uint32_t ri = (uint32_t)rankpre[p0 >> 5 < 2048 ? p0 >> 5 : 2048] + (uint32_t)__popc(k.tokw & ((1u << (p0 & 31)) - 1)) - (uint32_t)rankpre[r0 >> 5];
 			if (p0 >= n) ri = 0;
-			q0 = encode_quad<CHECK>(lltab, dtab, recbuf[par], ri, k.bytes.x, lit8 & 15, tok8 & 15, missing);
-			q1 = encode_quad<CHECK>(lltab, dtab, recbuf[par], ri, k.bytes.y, lit8 >> 4, tok8 >> 4, missing);
+			q0 = encode_quad<CHECK>(lltab, recbuf, ri, k.bytes.x, lit8 & 15, tok8 & 15, missing);
+			q1 = encode_quad<CHECK>(lltab, recbuf, ri, k.bytes.y, lit8 >> 4, tok8 >> 4, missing);
 		}
 		const uint32_t nbits = q0.nb + q1.nb;
 		uint32_t incl = nbits;
@@ -256,11 +273,8 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 		for (int w = 0; w < NT / 64; w++) { const uint32_t s = wsum[par][w]; if (w < wave) bitpos += s; roundbits += s; }
 		emit_quad(w_, q0, bitpos);
 		emit_quad(w_, q1, bitpos + q0.nb);
-		// the next round's records (asked for at the top of this round) into their LDS copy
-		if (more) {
-#pragma unroll
-			for (int j = 0; j < 3; j++) if (t + 256 * j < RECMAX) recbuf[par ^ 1][t + 256 * j] = nx.rec[j];
-		}
+		// the next round's records (asked for at the top of this round), coded, into the LDS copy: this round has read its own
+		if (more) stage_recs(nx);
 		__syncthreads();
 		// this window leaves (whole dwords) and is cleared; its last, partial dword opens the other
 		// window, which the next round fills (atomicOr: that round's lanes may be there already)
