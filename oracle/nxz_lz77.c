@@ -112,8 +112,17 @@
 #ifndef NXO_SECOND_MIN_TOKENS
 #define NXO_SECOND_MIN_TOKENS 3072   /* step 3b: tokens of a sub-block's first tile below which the later tiles do without second entries */
 #endif
+#ifndef NXO_MAXMATCH
+#define NXO_MAXMATCH 258             /* step 4: the longest match */
+#endif
+#ifndef NXO_CAND_WINDOW
+#define NXO_CAND_WINDOW NXO_WINDOW   /* step 4: the largest distance of a bucket candidate */
+#endif
+#ifndef NXO_DEEP_RUN
+#define NXO_DEEP_RUN 12              /* step 3: equal bytes p-(NXO_DEEP_RUN-4) .. p+3 that keep p out of the table */
+#endif
 #define MINMATCH 4
-#define MAXMATCH 258
+#define MAXMATCH NXO_MAXMATCH
 
 static inline uint32_t ld32(const uint8_t *p)
 {
@@ -173,6 +182,10 @@ static uint32_t walk(const uint8_t *w, uint32_t h, const uint16_t *mlen, const u
 
 /* debug taps */
 uint16_t *nxo_dbg_mlen, *nxo_dbg_mdist; uint32_t *nxo_dbg_x;
+/* per sub-block of the last nxo_lz77 call, four words: `text` of step 3c, the first tile's token count, and the
+ * use_second / lazy_max they led to for the later tiles (capacity: 4 words per sub-block of the call) */
+uint32_t *nxo_dbg_regime;
+static __thread uint32_t dbg_sub;
 
 /* one sub-block: w[0..h) window, w[h..h+n) block.  n <= NXO_SUBBLOCK, h <= NXO_WINDOW */
 /* Positions deep inside a run of one byte value -- the 12 bytes w[r-8 .. r+3] are all the same --
@@ -181,9 +194,9 @@ uint16_t *nxo_dbg_mlen, *nxo_dbg_mdist; uint32_t *nxo_dbg_x;
 static inline int deep_in_run(const uint8_t *w, uint32_t r)
 {
 	uint32_t k;
-	if (r < 8)
+	if (r < NXO_DEEP_RUN - 4)
 		return 0;
-	for (k = r - 8; k < r + 3; k++)
+	for (k = r - (NXO_DEEP_RUN - 4); k < r + 3; k++)
 		if (w[k] != w[k + 1])
 			return 0;
 	return 1;
@@ -241,9 +254,9 @@ static size_t lz77_subblock(const uint8_t *w, uint32_t h, uint32_t n, uint32_t *
 				uint32_t cand = deep ? 0 : head[hash4(v)], cand2 = deep || !use_second ? 0 : head2[hash4(v)];
 				uint32_t maxlen = end - r < MAXMATCH ? end - r : MAXMATCH;
 				uint32_t cap8 = maxlen < 8 ? maxlen : 8, a1 = 0, a2 = 0;
-				if (cand != 0 && r - (cand - 1) <= NXO_WINDOW && ld32(w + cand - 1) == v)
+				if (cand != 0 && r - (cand - 1) <= NXO_CAND_WINDOW && ld32(w + cand - 1) == v)
 					a1 = match_len(w + cand - 1, w + r, cap8);
-				if (cand2 != 0 && r - (cand2 - 1) <= NXO_WINDOW && ld32(w + cand2 - 1) == v)
+				if (cand2 != 0 && r - (cand2 - 1) <= NXO_CAND_WINDOW && ld32(w + cand2 - 1) == v)
 					a2 = match_len(w + cand2 - 1, w + r, cap8);
 				if (a2 > a1)
 					cand = cand2;
@@ -344,6 +357,10 @@ static size_t lz77_subblock(const uint8_t *w, uint32_t h, uint32_t n, uint32_t *
 		use_second = ntok >= NXO_SECOND_MIN_TOKENS && !text;
 		if (text && ntok >= NXO_SECOND_MIN_TOKENS)
 			lazy_max = 0;                      /* 3c */
+		if (nxo_dbg_regime) {
+			uint32_t *g = nxo_dbg_regime + 4 * dbg_sub;
+			g[0] = (uint32_t)text; g[1] = ntok; g[2] = (uint32_t)use_second; g[3] = lazy_max;
+		}
 	}
 	}
 	if (nxo_dbg_mlen) { memcpy(nxo_dbg_mlen, mlen, n * 2); memcpy(nxo_dbg_mdist, mdist, n * 2); }
@@ -353,12 +370,14 @@ static size_t lz77_subblock(const uint8_t *w, uint32_t h, uint32_t n, uint32_t *
 size_t nxo_lz77(const uint8_t *buf, size_t hist, size_t n, uint32_t *tok)
 {
 	size_t off = 0, ntok = 0;
+	dbg_sub = 0;
 	while (off < n) {
 		uint32_t bn = n - off < NXO_SUBBLOCK ? (uint32_t)(n - off) : NXO_SUBBLOCK;
 		size_t before = hist + off;
 		uint32_t h = before < NXO_WINDOW ? (uint32_t)before : NXO_WINDOW;
 		ntok += lz77_subblock(buf + before - h, h, bn, tok + ntok);
 		off += bn;
+		dbg_sub++;
 	}
 	return ntok;
 }

@@ -21,12 +21,16 @@ class InflateState(C.Structure):
                 ("spbc", C.c_size_t), ("tpbc", C.c_size_t), ("final_eob", C.c_int), ("err", C.c_int)]
 
 
+def _lz77_prototype(L):
+    L.nxo_lz77.restype = C.c_size_t
+    L.nxo_lz77.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32)]
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
-        L = C.CDLL(os.path.join(ROOT, "oracle", "libnxz_oracle.so"))
-        L.nxo_lz77.restype = C.c_size_t
-        L.nxo_lz77.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32)]
+        L = _lz77_prototype(C.CDLL(os.path.join(ROOT, "oracle", "libnxz_oracle.so")))
         L.nxo_encode_fixed.restype = C.c_uint64
         L.nxo_encode_fixed.argtypes = [C.POINTER(C.c_uint32), C.c_size_t, C.c_char_p, C.c_size_t]
         L.nxo_encode_dynamic.restype = C.c_uint64
@@ -50,11 +54,31 @@ def lib():
     return _lib
 
 
-def lz77(data: bytes, hist: int = 0):
+def lz77(data: bytes, hist: int = 0, L=None):
+    """L: another build of oracle/nxz_lz77.c (load_variant), the checker itself by default"""
     n = len(data) - hist
     tok = (C.c_uint32 * max(n, 1))()
-    nt = lib().nxo_lz77(data, hist, n, tok)
+    nt = (L or lib()).nxo_lz77(data, hist, n, tok)
     return tok, nt
+
+
+def load_variant(path):
+    """a shared object built from oracle/nxz_lz77.c with other -D values (tests/test_lz77_cases_host.py)"""
+    return _lz77_prototype(C.CDLL(path))
+
+
+def lz77_regime(data: bytes, hist: int = 0, L=None):
+    """lz77() with the nxo_dbg_regime tap: (tok, nt, [(text, first tile's tokens, use_second, lazy_max) per sub-block])"""
+    L = L or lib()
+    nsub = max(1, (len(data) - hist + 65535) // 65536)
+    buf = (C.c_uint32 * (4 * nsub))()
+    tap = C.c_void_p.in_dll(L, "nxo_dbg_regime")
+    tap.value = C.addressof(buf)
+    try:
+        tok, nt = lz77(data, hist, L)
+    finally:
+        tap.value = None
+    return tok, nt, [tuple(buf[4 * i:4 * i + 4]) for i in range(nsub)]
 
 
 def deflate_fixed(data: bytes, hist: int = 0):
