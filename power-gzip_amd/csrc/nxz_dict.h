@@ -1,5 +1,5 @@
 // nxz_dict.h -- the rules of a shared preset dictionary (nxz_dict_t, include/nxz_engine.h) as plain code that compiles
-// for the device (the kernels of the nxz_batch_*_dict calls) and for the host (nxz_engine.cpp, tests/native/dict_host.cpp).
+// for the device (the kernels of the nxz_batch_*_dict calls) and for the host (nxz_batch.cpp, tests/native/dict_host.cpp).
 //
 // A dictionary is `len` bytes that every job of a batch may refer to as if they stood in front of its data:
 //   inflate window   the last min(len, 32768) bytes -- what zlib's inflateSetDictionary keeps;

@@ -1,6 +1,6 @@
 """Batched inflate rate against the number of streams in the batch, for both kernels: a stream per
 lane (nxz_inflate_lanes.hip) and a stream per wave (nxz_inflate.hip).  The engine switches between
-them at NXZ_LANES_MIN streams (nxz_engine.cpp; NXZ_INFLATE_LANES_MIN overrides it for this sweep).
+them at NXZ_LANES_MIN streams (nxz_batch.cpp; NXZ_INFLATE_LANES_MIN overrides it for this sweep).
 usage: python tools/bench_inflate_sizes.py   (spawns one child per kernel)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
