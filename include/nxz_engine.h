@@ -489,6 +489,41 @@ int nxz_batch_decompress_framed_dict(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *
 				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Output sizes: what a batch of streams would produce, without decoding it
+ * ---------------------------------------------------------------------- */
+/* Every decompress call needs a target the caller has sized; raw deflate and zlib streams carry no length, and gzip's ISIZE is
+ * modulo 2^32 and not to be trusted.  This call walks the streams (block headers, tables, tokens: power-gzip_amd/csrc/
+ * nxz_inflate_size.hip, the rules in nxz_size.h) and writes results[i] = what nxz_batch_decompress would write for the same job
+ * with a target of dst_cap bytes -- cc, tpbc, tebc, spbc, subc and sfbt, bit 8 of sfbt (final EOB seen) and out_dhtlen in bits
+ * 16..27 included; a source that ends before the final block is CC 3 with the suspend fields.  The deviations:
+ *   - no checksums, no dst: crc = adler = 0.  dst is never read or written and may be NULL or misaligned; src may have any
+ *     alignment.  No dht_io is written.
+ *   - dst_cap is the limit: the walk stops with CC 13 at the token a decode would stop at.  0xffffffff = no limit; a stream of
+ *     more than 2^32 - 1 bytes of output then gets CC 13.  On CC 13 and on the error codes 66 / 67 / 68 only cc is specified.
+ *     NXZ_JOB_SUSPEND_WHEN_FULL is not honoured.
+ *   - hist_len (<= 32768) counts only as how far a distance may reach in front of the output: the hist_len bytes at src are
+ *     skipped, never read.  A job over [window][stream] -- and so any stream that uses a preset dictionary -- is sized by
+ *     setting hist_len to the window (the dictionary's inflate window: its last min(len, 32768) bytes); that is why there is no
+ *     _size_dict call.  resume != 0 or hist_len > 32768: cc = NXZ_CC_INVALID_OP, every other field 0.
+ * The two-pass recipe: size, an exclusive prefix sum of tpbc rounded up to 16, jobs, decode.
+ * Asynchronous on `stream`: no host wait, no allocation beyond the stream's scratch.
+ * Speed: not measured yet.  tools/bench_size.py runs this call beside nxz_batch_decompress on the same streams and writes
+ * profiles/r10_size.txt; a size query slower than the decode it spares is not worth having, so look there before relying on it. */
+int nxz_batch_decompress_size(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n,
+			      nxz_batch_result_t *results, void *stream);
+
+/* The same for zlib / gzip streams: the header kernel of nxz_batch_decompress_framed (with `dict`, which may be NULL, that of
+ * nxz_batch_decompress_framed_dict and its DICTID rules: a zlib job that names the dictionary is walked with the dictionary's
+ * window as its reach), the size walk on the deflate data, and a trailer step that reads frames[i].check / isize and sets end.
+ * Every NXZ_FRAME_* status is decided as in the decoding calls -- except NXZ_FRAME_BAD_CHECK, which cannot be detected without the
+ * output: a job that a decode would call BAD_CHECK is reported as it would be if its check were right, that is NXZ_FRAME_OK, or
+ * NXZ_FRAME_BAD_LENGTH when gzip's ISIZE differs from tpbc.  frames[i].check is the trailer's value as read.  jobs[].dst is not
+ * touched; resume and hist_len must be 0 (NXZ_FRAME_BAD_HEADER). */
+int nxz_batch_decompress_size_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *dict /* may be NULL */,
+				     const nxz_batch_job_t *jobs, size_t n,
+				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
+
+/* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */
 /* The member index of a BGZF image in DEVICE memory (found as nxz_batch_unpack_gzip finds the members):

@@ -663,6 +663,56 @@ extern "C" int nxz_batch_decompress_framed_dict(nxz_ctx_t *c, int fmt, const nxz
 	return framed_locked(c, fmt, jobs, n, results, frames, s, dict);
 }
 
+// ---------------------------------------------------------------------------
+// Output sizes (nxz_inflate_size.hip): what the streams would produce, a wavefront each, all on `s`, nothing waits.  From 128
+// streams on the long ones start first (the order is this stream's scratch, as for the decode routes).  The caller holds no lease.
+// ---------------------------------------------------------------------------
+static int batch_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint32_t dict_window, hipStream_t s)
+{
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
+	}) : nullptr;
+	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
+	const int rc = nxz_launch_inflate_size(jobs, n, results, order, dict_window, s);
+	if (rc) { set_err("inflate size launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+extern "C" int nxz_batch_decompress_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, void *stream)
+{
+	if (!c || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	return batch_size(c, jobs, n, results, 0, (hipStream_t)stream);
+}
+
+// header kernel (the framed decode's own, with the dictionary's DICTID when there is one) -> the size walk on the derived jobs ->
+// the trailer step without the checksum comparison.  frame_use[s] guards the derived jobs, as in framed_locked.
+extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || (dict && dict->device != c->device) || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	nxz_batch_job_t *const derived = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_FRAME_JOBS].grow(s, n * sizeof(nxz_batch_job_t));
+		return sc.buf[BUF_FRAME_JOBS].as<nxz_batch_job_t>();
+	});
+	if (!derived) return -ENOMEM;
+	int rc = dict ? nxz_launch_frame_header_dict(fmt, jobs, n, frames, derived, dict->id, s) : nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
+	if (rc) { set_err("frame header launch", (hipError_t)rc); return -EIO; }
+	// (without a dictionary the header kernel sets no NXZ_JOB_NO_DICT, and there is no window to withhold: 0)
+	if ((rc = batch_size(c, derived, n, results, dict ? dict->win : 0, s)) != 0) return rc;
+	rc = nxz_launch_size_trailer(jobs, n, results, frames, s);
+	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
 // The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then
 // ONE wait for ctl = candidates, members, bytes covered, sum of ISIZE.  The caller holds c->frame_use[s].
 static int bgzf_discover_locked(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, size_t max_members,

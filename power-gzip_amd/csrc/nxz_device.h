@@ -130,6 +130,12 @@ int nxz_launch_pack_zlib_dict(const nxz_batch_job_t *jobs, const nxz_batch_resul
 			      uint64_t *offsets, uint8_t *packed, hipStream_t stream);
 int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames, nxz_batch_job_t *derived,
 				 uint32_t dictid, hipStream_t stream);
+/* nxz_inflate_size.hip: what the streams would produce, a wavefront each, nothing written but results (nxz_size.h has the rules).
+ * order: NULL, or nxz_launch_order_by_length's; dict_window: how far every job's distances may reach besides its own hist_len
+ * (a shared dictionary's inflate window; jobs that say NXZ_JOB_NO_DICT do not get it) */
+int nxz_launch_inflate_size(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const uint32_t *order,
+			    uint32_t dict_window, hipStream_t stream);
+int nxz_launch_size_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);   /* nxz_launch_frame_trailer without the checksum comparison */
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

@@ -136,6 +136,10 @@ def load_library():
                                                C.c_void_p]
         L.nxz_batch_decompress_framed_dict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        # output sizes without a decode
+        L.nxz_batch_decompress_size.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_batch_decompress_size_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -309,6 +313,30 @@ class Engine:
         rc = self.L.nxz_batch_decompress_framed_dict(self.ctx, fmt, d.handle, jobs.data_ptr(), n, results.data_ptr(), frames.data_ptr(),
                                                      self.stream_handle())
         self._check(rc, "nxz_batch_decompress_framed_dict")
+        return results, frames
+
+    # ---- output sizes: what the streams would produce, nothing decoded, dst never touched ----
+    def decompress_size(self, jobs, n, results=None):
+        """nxz_batch_decompress_size: results[i] as decompress() would report for a target of jobs[i].dst_cap bytes (0xffffffff: no
+        limit), crc = adler = 0.  jobs[i].dst may be 0; hist_len only says how far a distance may reach."""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        self._check(self.L.nxz_batch_decompress_size(self.ctx, jobs.data_ptr(), n, results.data_ptr(), self.stream_handle()),
+                    "nxz_batch_decompress_size")
+        return results
+
+    def decompress_size_framed(self, fmt, jobs, n, d=None, results=None, frames=None):
+        """nxz_batch_decompress_size_framed: as decompress_framed / decompress_framed_dict (d: a Dict or None) without the decode;
+        FRAME_BAD_CHECK cannot occur.  Returns (results, frames)."""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if frames is None:
+            frames = t.empty(n * FRAME_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_decompress_size_framed(self.ctx, fmt, d.handle if d is not None else None, jobs.data_ptr(), n,
+                                                     results.data_ptr(), frames.data_ptr(), self.stream_handle())
+        self._check(rc, "nxz_batch_decompress_size_framed")
         return results, frames
 
     def frames_to_host(self, frames):
