@@ -524,6 +524,55 @@ int nxz_batch_decompress_size_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *
 				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
 
 /* ------------------------------------------------------------------------
+ * One stream per device buffer: batched deflate of buffers of any length
+ * ---------------------------------------------------------------------- */
+/* The compress-side counterpart of the framed decode: a batch of DEVICE buffers of any length, each written as ONE raw, zlib or
+ * gzip stream in DEVICE memory -- what nxz_deflate_host[_hist] does for one host buffer, without leaving the device (a Parquet
+ * page, a Zarr or HDF5 chunk, a tensor).  fc = NXZ_FC_COMPRESS_FHT or NXZ_FC_COMPRESS_DHTGEN (else -EINVAL).  hist_max as in
+ * nxz_deflate_host_hist: rounded down to a multiple of 16, 32768 at most; a block carries B = 65536 - H source bytes and block k
+ * sees the min(H, k * B) bytes of the same buffer in front of it.  The deflate data of stream i is byte for byte what
+ * nxz_deflate_host_hist(fc, buffer i, final = 1, hist_max, prev = NULL) writes: the same cut, the same empty stored block behind a
+ * block that ends inside a byte, the same stored-block fallback, BFINAL on the last block.  Around it:
+ *   NXZ_FMT_RAW    nothing
+ *   NXZ_FMT_ZLIB   78 and FLG with FLEVEL from `level` (-1, 0..9: as nxz_batch_pack_zlib) in front, the Adler-32 big-endian behind
+ *   NXZ_FMT_GZIP   1f 8b 08 00 00 00 00 00 04 03 in front, CRC-32 and ISIZE = src_len mod 2^32 little-endian behind
+ * A buffer of length 0 gives the body 01 00 00 ff ff and blocks = 0.  `level` chooses nothing but FLEVEL.
+ * jobs is a HOST array (the caller knows its buffers' sizes) and may be reused as soon as the call returns: what the engine needs
+ * of it goes into pinned staging of the stream's scratch, and the host work is one pass over the streams, not over their blocks.
+ * results is a DEVICE array.  A stream that is refused (results[i].cc) costs nothing and leaves its neighbours alone.
+ * The blocks of the whole batch go through nxz_batch_compress in chunks of NXZ_STREAMS_CHUNK blocks (environment, read at every
+ * call; default 4096, about 300 MB of scratch for the blocks' outputs before they are packed); a stream may straddle chunks, and
+ * the output does not depend on the chunk size.  On the device: job expansion, layout and checksum joins, packing with framing
+ * (power-gzip_amd/csrc/nxz_streams.hip, the rules in nxz_streams.h).
+ * Asynchronous on `stream`: no host wait and no device allocation once the stream's scratch has grown to the batch.
+ * Returns 0; -EINVAL (ctx, fc, fmt, level, jobs or results NULL with n != 0); -ENODEV in a forked child; -E2BIG when the batch
+ * holds 2^31 blocks (or streams) or more; -ENOMEM when scratch cannot be had.
+ * Speed (tools/bench_streams.py, profiles/r11_streams.txt; zlib, DHTGEN, hist_max 0): 0.93 of the rate of nxz_batch_compress +
+ * nxz_batch_pack_zlib on the same bytes cut into 64 KiB jobs, a member per block (94 against 102 GiB/s for 4096 streams of 1 MiB and
+ * for 65 536 of 64 KiB; one stream of 1 GiB: 0.77).  With hist_max 32768 -- twice the jobs -- 0.71 to 0.76, one stream 0.53. */
+enum { NXZ_FMT_RAW = 0 };            /* beside NXZ_FMT_ZLIB = 1, NXZ_FMT_GZIP = 2 */
+typedef struct nxz_stream_job {      /* HOST array */
+	const uint8_t *src;          /* DEVICE, 16-byte aligned */
+	uint8_t       *dst;          /* DEVICE, any alignment */
+	uint64_t       src_len;      /* any length, 0 included */
+	uint64_t       dst_cap;      /* >= nxz_deflate_stream_bound(src_len, hist_max, fmt) */
+} nxz_stream_job_t;
+typedef struct nxz_stream_result {   /* DEVICE array, written by the device, 32 bytes */
+	uint32_t cc;                 /* 0; NXZ_CC_TARGET_SPACE (dst_cap below the bound: out_len = the bound, dst untouched);
+	                                NXZ_CC_INVALID_OP (src NULL with src_len != 0, src not 16-byte aligned, dst NULL: dst untouched) */
+	uint32_t blocks;             /* compress jobs the stream was cut into */
+	uint64_t out_len;            /* bytes at dst: header + deflate data + trailer */
+	uint32_t crc, adler;         /* of the source, from 0 / 1 */
+	uint32_t stored;             /* blocks that went out as stored blocks */
+	uint32_t reserved;
+} nxz_stream_result_t;
+/* nxz_deflate_host_bound_hist(src_len, hist_max) + 0 (raw) / 6 (zlib) / 18 (gzip) */
+size_t nxz_deflate_stream_bound(uint64_t src_len, uint32_t hist_max, int fmt);
+int nxz_batch_deflate_streams(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32_t hist_max,
+			      const nxz_stream_job_t *jobs /* HOST */, size_t n,
+			      nxz_stream_result_t *results /* DEVICE */, void *stream);
+
+/* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */
 /* The member index of a BGZF image in DEVICE memory (found as nxz_batch_unpack_gzip finds the members):

@@ -1,6 +1,7 @@
 // nxz_batch.cpp -- the batched, device-resident interface of include/nxz_engine.h: the compress and inflate batches and which
 // kernels they get, their dictionary, framed and BGZF forms, table generation, wrap and the pack forms, and the diagnostics.
 #include "nxz_ctx.h"
+#include "nxz_streams.h"
 
 // ---------------------------------------------------------------------------
 // batched, device-resident interface
@@ -710,6 +711,111 @@ extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz
 	if ((rc = batch_size(c, derived, n, results, dict ? dict->win : 0, s)) != 0) return rc;
 	rc = nxz_launch_size_trailer(jobs, n, results, frames, s);
 	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+// ---------------------------------------------------------------------------
+// One stream per device buffer (nxz_streams.hip, the rules in nxz_streams.h).  The host makes one pass over the streams -- the
+// refusals and the block prefix first[n + 1] -- into pinned staging, uploads it with the descriptors, and queues per chunk of
+// NXZ_STREAMS_CHUNK blocks: expand -> nxz_batch_compress on the device jobs -> layout and checksum joins -> pack; a prologue in
+// front (headers, state) and an epilogue behind (empty streams, trailers, results).  Everything goes on `s`.
+// No host wait: once the stream's scratch holds a batch of this size there is no hipStreamSynchronize, hipMalloc or hipFree on
+// this path (DevBuf::grow and nxz_batch_compress's chunk only act when they must grow).  The one wait there can be is for the
+// UPLOAD of the call before the last on this stream, whose pinned staging this call fills again (Scratch::h_up: two in turn, an
+// event behind each upload); a caller who queues three calls faster than the device takes two uploads meets it, no other.
+// frame_use[s] guards BUF_STREAMS and the staging, as it guards the derived jobs of the framed calls: nxz_batch_compress takes
+// the scratch lease itself.
+// ---------------------------------------------------------------------------
+static uint32_t streams_chunk()
+{
+	const char *e = getenv("NXZ_STREAMS_CHUNK");                        // (read at every call: the tests switch it)
+	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
+	return v ? (uint32_t)std::min<uint64_t>(v, 65536) : NXZ_STREAMS_CHUNK_DEFAULT;
+}
+
+extern "C" size_t nxz_deflate_stream_bound(uint64_t src_len, uint32_t hist_max, int fmt)
+{
+	return (size_t)nxz_streams_bound(src_len, hist_max, fmt);
+}
+
+extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
+					 nxz_stream_result_t *results, void *stream)
+{
+	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !nxz_streams_fmt_ok(fmt) || level < -1 || level > 9 ||
+	    (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	if (n >= (1u << 31)) return -E2BIG;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max), ns = (uint32_t)n;
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	// what is uploaded: [descriptors][first], the same layout in the staging and in the device buffer
+	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), up_bytes = o_first + (n + 1) * sizeof(uint32_t);
+	// this call's staging: the upload that read it last must have run
+	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
+	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
+	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), return -ENOMEM);
+	else HIPCHK(hipEventSynchronize(st.ev), return -EIO);
+	if (st.cap < up_bytes) {
+		if (st.h) (void)hipHostFree(st.h);
+		st.h = nullptr; st.cap = 0;
+		if (hipHostMalloc((void **)&st.h, up_bytes) == hipSuccess) st.cap = up_bytes;
+		else { (void)hipGetLastError(); st.h = nullptr; }
+	}
+	with_scratch(c, s, [&](nxz_ctx::Scratch &r) { r.h_up[st.k] = st.h; r.h_up_cap[st.k] = st.cap; r.up_ev[st.k] = st.ev; return 0; });
+	if (!st.h) return -ENOMEM;
+	// one pass over the streams: a refused stream gets no blocks
+	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st.h;
+	uint32_t *const h_first = (uint32_t *)(st.h + o_first);
+	memcpy(h_desc, jobs, n * sizeof(nxz_stream_job_t));
+	uint64_t total = 0;
+	for (size_t i = 0; i < n; i++) {
+		h_first[i] = (uint32_t)total;
+		if (!nxz_streams_refusal(&jobs[i], hist_max, fmt)) total += nxz_streams_blocks(jobs[i].src_len, B);
+		if (total >= (1ull << 31)) return -E2BIG;
+	}
+	h_first[n] = (uint32_t)total;
+	const uint32_t nblk = (uint32_t)total, C = std::min(streams_chunk(), nblk);
+	const size_t o_state = up(up_bytes), o_jobs = o_state + up(n * sizeof(nxz_stream_state_t)), o_res = o_jobs + up((size_t)C * sizeof(nxz_batch_job_t)),
+		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
+		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), d_bytes = o_slots + (size_t)C * NXZ_STREAMS_SLOT;
+	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
+		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
+		return r.buf[BUF_STREAMS].p;
+	});
+	if (!d) return -ENOMEM;
+	const nxz_stream_job_t *const d_desc = (const nxz_stream_job_t *)d;
+	const uint32_t *const d_first = (const uint32_t *)(d + o_first);
+	nxz_stream_state_t *const d_state = (nxz_stream_state_t *)(d + o_state);
+	nxz_batch_job_t *const d_jobs = (nxz_batch_job_t *)(d + o_jobs);
+	nxz_batch_result_t *const d_res = (nxz_batch_result_t *)(d + o_res);
+	uint32_t *const d_owner = (uint32_t *)(d + o_owner);
+	uint64_t *const d_off = (uint64_t *)(d + o_off);
+	uint8_t *const d_slots = d + o_slots;
+	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
+	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
+	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
+	int rc = nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s);
+	if (rc) { set_err("streams prologue launch", (hipError_t)rc); return -EIO; }
+	const uint32_t op_block = nxz_crc_shift_op(B);
+	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
+	for (uint32_t b0 = 0; b0 < nblk; b0 += C) {
+		const uint32_t m = std::min(C, nblk - b0);
+		while (h_first[i_lo + 1] <= b0) i_lo++;
+		uint32_t i_hi = i_lo;
+		while (h_first[i_hi + 1] < b0 + m) i_hi++;
+		rc = nxz_launch_streams_expand(d_desc, d_first, ns, b0, m, hist_max, d_slots, d_jobs, d_owner, s);
+		if (rc) { set_err("streams expand launch", (hipError_t)rc); return -EIO; }
+		if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
+		rc = nxz_launch_streams_layout(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
+		if (!rc) rc = nxz_launch_streams_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, s);
+		if (rc) { set_err("streams pack launch", (hipError_t)rc); return -EIO; }
+		i_lo = i_hi;
+	}
+	rc = nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s);
+	if (rc) { set_err("streams epilogue launch", (hipError_t)rc); return -EIO; }
 	return 0;
 }
 

@@ -81,6 +81,7 @@ enum ScratchBuf {
 	BUF_BGZF,           // nxz_batch_unpack_gzip: the discovery's candidates, jump tables and the members' jobs
 	BUF_RNG,            // nxz_bgzf_read_ranges: the map's per-range and per-member arrays
 	BUF_RNG_SLOTS,      // ... a chunk of decoded members (16-byte aligned slots), their jobs, frames and results
+	BUF_STREAMS,        // nxz_batch_deflate_streams: descriptors, block prefix and state of the streams; jobs, results, owners, offsets and output slots of a chunk
 	BUF_COUNT
 };
 
@@ -107,6 +108,12 @@ struct nxz_ctx {
 		uint8_t *d_fuse = nullptr;                // the fused dynamic-Huffman form: two token slots and two table slots per workgroup (nxz_lz77.hip gen::)
 		size_t chunk_cap = 0;
 		size_t chunk_limit = 0;                   // jobs per chunk the device had room for when a larger chunk could not be had (0: no such failure yet)
+		// nxz_batch_deflate_streams: pinned staging for the descriptors and the block prefix, two of them in turn -- a call returns
+		// before its upload has run, so the next call fills the other one; up_ev[k] is recorded behind the upload from h_up[k]
+		uint8_t *h_up[2] = { nullptr, nullptr };
+		size_t h_up_cap[2] = { 0, 0 };
+		hipEvent_t up_ev[2] = { nullptr, nullptr };
+		unsigned up_turn = 0;
 		void release_chunk() {
 			if (d_tokens) (void)hipFree(d_tokens);                       // (d_gen and d_counts lie inside it)
 			d_tokens = nullptr; d_gen = nullptr; d_counts = nullptr; chunk_cap = 0;
@@ -130,6 +137,10 @@ struct nxz_ctx {
 			if (d_tokens) (void)hipFree(d_tokens);                       // (d_gen and d_counts lie inside it)
 			if (d_cand2) (void)hipFree(d_cand2);
 			if (d_fuse) (void)hipFree(d_fuse);
+			for (int k = 0; k < 2; k++) {
+				if (h_up[k]) (void)hipHostFree(h_up[k]);
+				if (up_ev[k]) (void)hipEventDestroy(up_ev[k]);
+			}
 			*this = Scratch();
 		}
 	};

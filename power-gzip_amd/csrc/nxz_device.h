@@ -136,6 +136,21 @@ int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n,
 int nxz_launch_inflate_size(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const uint32_t *order,
 			    uint32_t dict_window, hipStream_t stream);
 int nxz_launch_size_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);   /* nxz_launch_frame_trailer without the checksum comparison */
+/* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
+ * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
+ * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */
+typedef struct nxz_stream_state { uint64_t written, len_done; uint32_t crc, adler, stored, cc; } nxz_stream_state_t;
+int nxz_launch_streams_prologue(const nxz_stream_job_t *desc, uint32_t n, uint32_t hist_max, int fmt, int level,
+				nxz_stream_state_t *state, hipStream_t stream);
+int nxz_launch_streams_expand(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t b0, uint32_t m,
+			      uint32_t hist_max, uint8_t *slots, nxz_batch_job_t *jobs, uint32_t *owner, hipStream_t stream);
+int nxz_launch_streams_layout(const uint32_t *first, uint32_t i_lo, uint32_t streams, uint32_t b0, uint32_t m,
+			      const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, uint32_t hist_max, uint32_t op_block,
+			      nxz_stream_state_t *state, uint64_t *offsets, hipStream_t stream);
+int nxz_launch_streams_pack(const nxz_stream_job_t *desc, const uint32_t *first, const uint32_t *owner, uint32_t b0, uint32_t m,
+			    const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, const uint64_t *offsets, hipStream_t stream);
+int nxz_launch_streams_epilogue(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
+				const nxz_stream_state_t *state, nxz_stream_result_t *results, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

@@ -1,0 +1,226 @@
+// nxz_streams.hip -- the kernels around the compress batch of nxz_batch_deflate_streams (include/nxz_engine.h): a batch of device
+// buffers of any length, each written as ONE raw, zlib or gzip stream.  The rules (block plan, bound, framing, checksum joins) are
+// nxz_streams.h; a block is laid into its stream by pack_block (nxz_pack_block.h), as nxz_deflate_host's kernels lay theirs.
+//
+//   prologue   a thread per stream: refusals, the header bytes, the stream's running state
+//   expand     a thread per block of a chunk: whose block it is (upper bound in the streams' block prefix), its compress job
+//   -- nxz_batch_compress on those jobs --
+//   layout     a wavefront per stream the chunk touches: where each of its blocks goes (exclusive prefix of the pieces' sizes,
+//              continued from the stream's `written`), CRC-32 and Adler-32 of the chunk's part joined onto the stream's
+//   pack       a workgroup per block: pack_block
+//   epilogue   a thread per stream: the empty streams' body, the trailers, results[]
+// A stream is indexed by a uint32_t everywhere (a batch holds fewer than 2^31 streams and blocks).
+#include <hip/hip_runtime.h>
+#include "nxz_device.h"
+#include "nxz_streams.h"
+#include "nxz_pack_block.h"
+
+namespace nxzst {
+
+// the stream that block g of the batch belongs to: the i with first[i] <= g < first[i + 1] (streams without blocks are passed over)
+__device__ inline uint32_t owner_of(const uint32_t *__restrict__ first, uint32_t n, uint32_t g)
+{
+	uint32_t lo = 0, hi = n - 1;
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (first[mid + 1] > g) hi = mid; else lo = mid + 1;
+	}
+	return lo;
+}
+
+__global__ __launch_bounds__(256) void prologue_kernel(const nxz_stream_job_t *__restrict__ desc, uint32_t n, uint32_t hist_max, int fmt, int level,
+							 nxz_stream_state_t *__restrict__ state)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const nxz_stream_job_t j = desc[i];
+	nxz_stream_state_t st;
+	st.cc = nxz_streams_refusal(&j, hist_max, fmt);
+	st.written = 0; st.len_done = 0; st.crc = 0; st.adler = 1; st.stored = 0;
+	if (!st.cc) {
+		uint8_t h[10];
+		const uint32_t hl = nxz_streams_header(fmt, level, h);
+		for (uint32_t k = 0; k < hl; k++) j.dst[k] = h[k];
+		st.written = hl;
+	}
+	state[i] = st;
+}
+
+__global__ __launch_bounds__(256) void expand_kernel(const nxz_stream_job_t *__restrict__ desc, const uint32_t *__restrict__ first, uint32_t n,
+						       uint32_t b0, uint32_t m, uint32_t B, uint32_t H, uint8_t *__restrict__ slots,
+						       nxz_batch_job_t *__restrict__ jobs, uint32_t *__restrict__ owner)
+{
+	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+	if (t >= m) return;
+	const uint32_t g = b0 + t, i = owner_of(first, n, g);
+	const uint64_t k = g - first[i];
+	const nxz_stream_job_t d = desc[i];
+	const uint32_t hk = nxz_streams_block_window(k, B, H);
+	nxz_batch_job_t j;
+	j.src = d.src + nxz_streams_block_start(k, B) - hk;
+	j.dst = slots + (size_t)t * NXZ_STREAMS_SLOT;
+	j.src_len = hk + nxz_streams_block_len(d.src_len, k, B);
+	j.hist_len = hk;
+	j.dst_cap = NXZ_STREAMS_SLOT;
+	j.in_crc = 0; j.in_adler = 1;
+	j.dht_index = 0; j.resume = 0; j.reserved = 0;
+	jobs[t] = j;
+	owner[t] = i;
+}
+
+__device__ inline uint32_t wave_xor(uint32_t v)
+{
+	for (int d = 32; d; d >>= 1) v ^= __shfl_xor(v, d);
+	return v;
+}
+__device__ inline uint64_t wave_sum(uint64_t v)
+{
+	for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
+	return v;
+}
+
+// One wavefront per stream of [i_lo, i_lo + gridDim.x); the stream's blocks inside the chunk [b0, b0 + m), 64 at a time, a lane each.
+// Sizes and the Adler sums are prefix sums over the lanes.  The CRC needs no scan: every block but a stream's last has B bytes, so
+// a lane knows how many bytes lie behind its block in this part and moves its block's CRC over them itself (op_block = the operator
+// of B bytes, made once by the host; powers of it by square-and-multiply); the moved CRCs are XORed together.
+__global__ __launch_bounds__(64) void layout_kernel(const uint32_t *__restrict__ first, uint32_t i_lo, uint32_t b0, uint32_t m,
+						      const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
+						      uint32_t B, uint32_t op_block, nxz_stream_state_t *__restrict__ state, uint64_t *__restrict__ offsets)
+{
+	const uint32_t i = i_lo + blockIdx.x, lane = threadIdx.x;
+	const uint32_t f0 = first[i], f1 = first[i + 1];
+	const uint32_t lo = f0 > b0 ? f0 : b0, hi = f1 < b0 + m ? f1 : b0 + m;
+	if (lo >= hi) return;
+	const nxz_stream_state_t st = state[i];
+	const uint32_t M = NXZ_ADLER_BASE;
+	// the part's last block: the only one that may be short
+	const uint32_t last_len = jobs[hi - 1 - b0].src_len - jobs[hi - 1 - b0].hist_len;
+	const uint32_t tail = last_len == B ? 0 : last_len, last_full = last_len == B ? 1 : 0;
+	uint64_t base = st.written, adler_b = 0;
+	uint32_t base_da = ((st.adler & 0xffff) + M - 1) % M;                 // (Adler's low sum so far) - 1
+	uint32_t crc_part = 0, stored = 0;
+	for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
+		const uint32_t g = i0 + lane;
+		const bool valid = g < hi;
+		uint32_t size = 0, da = 0, len = 0, crc = 0, bsum = 0;
+		bool is_stored = false;
+		if (valid) {
+			const nxz_batch_job_t job = jobs[g - b0];
+			const nxz_batch_result_t r = results[g - b0];
+			const nxz::StreamPiece p = nxz::stream_piece(job, r, g == f1 - 1);
+			size = p.size; len = p.len; is_stored = p.stored;
+			crc = r.crc; da = ((r.adler & 0xffff) + M - 1) % M; bsum = r.adler >> 16;
+		}
+		uint64_t incl = size;
+		uint32_t incl_da = da;
+		for (uint32_t d = 1; d < 64; d <<= 1) {
+			const uint64_t v = __shfl_up(incl, d);
+			const uint32_t w = __shfl_up(incl_da, d);
+			if (lane >= d) { incl += v; incl_da += w; }
+		}
+		if (valid) {
+			offsets[g - b0] = base + incl - size;
+			// the bytes behind this block in the part: hi - 1 - g blocks, all of B bytes but perhaps the last
+			const uint32_t behind = hi - 1 - g;
+			const uint32_t op = behind ? nxz_crc_blocks_op(op_block, (uint64_t)behind - 1 + last_full, tail) : 0x80000000u;
+			crc_part ^= nxz_gf2_mul32(crc, op);
+			const uint32_t P = (base_da + incl_da - da) % M;              // (the low sum in front of this block) - 1
+			adler_b += (bsum + (uint64_t)(len % M) * P) % M;
+		}
+		base += __shfl(incl, 63);
+		base_da = (base_da + __shfl(incl_da, 63)) % M;
+		stored += (uint32_t)__popcll(__ballot(valid && is_stored));
+	}
+	crc_part = wave_xor(crc_part);
+	adler_b = wave_sum(adler_b);
+	if (lane == 0) {
+		const uint32_t cnt = hi - lo;
+		const uint64_t bytes = (uint64_t)(cnt - 1) * B + last_len;
+		nxz_stream_state_t o = st;
+		o.written = base;
+		o.len_done = st.len_done + bytes;
+		o.crc = nxz_crc_join(st.crc, crc_part, nxz_crc_blocks_op(op_block, (uint64_t)cnt - 1 + last_full, tail));
+		o.adler = (uint32_t)(((st.adler >> 16) + adler_b) % M) << 16 | (base_da + 1) % M;
+		o.stored = st.stored + stored;
+		state[i] = o;
+	}
+}
+
+__global__ __launch_bounds__(256) void pack_kernel(const nxz_stream_job_t *__restrict__ desc, const uint32_t *__restrict__ first,
+						     const uint32_t *__restrict__ owner, uint32_t b0, const nxz_batch_job_t *__restrict__ jobs,
+						     const nxz_batch_result_t *__restrict__ results, const uint64_t *__restrict__ offsets)
+{
+	const uint32_t t = blockIdx.x, i = owner[t];
+	nxz::pack_block(jobs[t], results[t], b0 + t == first[i + 1] - 1, desc[i].dst + offsets[t]);
+}
+
+__global__ __launch_bounds__(256) void epilogue_kernel(const nxz_stream_job_t *__restrict__ desc, const uint32_t *__restrict__ first, uint32_t n,
+							 uint32_t hist_max, int fmt, const nxz_stream_state_t *__restrict__ state,
+							 nxz_stream_result_t *__restrict__ results)
+{
+	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const nxz_stream_job_t j = desc[i];
+	const nxz_stream_state_t st = state[i];
+	nxz_stream_result_t r;
+	r.cc = st.cc; r.blocks = 0; r.out_len = 0; r.crc = 0; r.adler = 0; r.stored = 0; r.reserved = 0;
+	if (st.cc) {
+		if (st.cc == NXZ_CC_TARGET_SPACE) r.out_len = nxz_streams_bound(j.src_len, hist_max, fmt);
+		results[i] = r;
+		return;
+	}
+	uint64_t at = st.written;
+	if (!j.src_len) {
+		uint8_t e[NXZ_STREAMS_EMPTY_LEN];
+		nxz_streams_empty(e);
+		for (uint32_t k = 0; k < NXZ_STREAMS_EMPTY_LEN; k++) j.dst[at + k] = e[k];
+		at += NXZ_STREAMS_EMPTY_LEN;
+	}
+	uint8_t tr[8];
+	const uint32_t tl = nxz_streams_trailer(fmt, st.crc, st.adler, j.src_len, tr);
+	for (uint32_t k = 0; k < tl; k++) j.dst[at + k] = tr[k];
+	r.blocks = first[i + 1] - first[i];
+	r.out_len = at + tl;
+	r.crc = st.crc; r.adler = st.adler; r.stored = st.stored;
+	results[i] = r;
+}
+
+} // namespace nxzst
+
+extern "C" int nxz_launch_streams_prologue(const nxz_stream_job_t *desc, uint32_t n, uint32_t hist_max, int fmt, int level,
+					   nxz_stream_state_t *state, hipStream_t stream)
+{
+	hipLaunchKernelGGL(nxzst::prologue_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, desc, n, hist_max, fmt, level, state);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_streams_expand(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t b0, uint32_t m,
+					 uint32_t hist_max, uint8_t *slots, nxz_batch_job_t *jobs, uint32_t *owner, hipStream_t stream)
+{
+	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max);
+	hipLaunchKernelGGL(nxzst::expand_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, desc, first, n, b0, m, B, H, slots, jobs, owner);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_streams_layout(const uint32_t *first, uint32_t i_lo, uint32_t streams, uint32_t b0, uint32_t m,
+					 const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, uint32_t hist_max, uint32_t op_block,
+					 nxz_stream_state_t *state, uint64_t *offsets, hipStream_t stream)
+{
+	hipLaunchKernelGGL(nxzst::layout_kernel, dim3(streams), dim3(64), 0, stream, first, i_lo, b0, m, jobs, results,
+			   nxz_streams_block_bytes(hist_max), op_block, state, offsets);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_streams_pack(const nxz_stream_job_t *desc, const uint32_t *first, const uint32_t *owner, uint32_t b0, uint32_t m,
+				       const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, const uint64_t *offsets, hipStream_t stream)
+{
+	hipLaunchKernelGGL(nxzst::pack_kernel, dim3(m), dim3(256), 0, stream, desc, first, owner, b0, jobs, results, offsets);
+	return (int)hipGetLastError();
+}
+
+extern "C" int nxz_launch_streams_epilogue(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
+					   const nxz_stream_state_t *state, nxz_stream_result_t *results, hipStream_t stream)
+{
+	hipLaunchKernelGGL(nxzst::epilogue_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, desc, first, n, hist_max, fmt, state, results);
+	return (int)hipGetLastError();
+}

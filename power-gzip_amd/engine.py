@@ -35,12 +35,19 @@ assert JOB_DTYPE.itemsize == 48 and RESULT_DTYPE.itemsize == 32 and DHT_DTYPE.it
 
 # framed streams (include/nxz_engine.h: nxz_batch_decompress_framed / nxz_batch_unpack_gzip)
 FMT_ZLIB, FMT_GZIP, FMT_AUTO = 1, 2, 3
+FMT_RAW = 0                         # nxz_batch_deflate_streams only: no framing
 (FRAME_OK, FRAME_BAD_HEADER, FRAME_BAD_METHOD, FRAME_NEED_DICT, FRAME_BAD_HCRC, FRAME_TRUNCATED, FRAME_DEFLATE,
  FRAME_BAD_CHECK, FRAME_BAD_LENGTH) = range(9)
 FRAME_DTYPE = np.dtype([("status", "<u4"), ("format", "<u4"), ("hdr_len", "<u4"), ("end", "<u4"), ("check", "<u4"),
                         ("isize", "<u4"), ("mtime", "<u4"), ("dictid", "<u4"), ("extra_off", "<u4"), ("extra_len", "<u4"),
                         ("name_off", "<u4"), ("comment_off", "<u4"), ("flg", "u1"), ("xfl", "u1"), ("os", "u1"), ("cinfo", "u1")])
 assert FRAME_DTYPE.itemsize == 52
+
+# one stream per device buffer (include/nxz_engine.h: nxz_batch_deflate_streams)
+STREAM_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u8"), ("dst_cap", "<u8")])
+STREAM_RESULT_DTYPE = np.dtype([("cc", "<u4"), ("blocks", "<u4"), ("out_len", "<u8"), ("crc", "<u4"), ("adler", "<u4"),
+                                ("stored", "<u4"), ("reserved", "<u4")])
+assert STREAM_JOB_DTYPE.itemsize == 32 and STREAM_RESULT_DTYPE.itemsize == 32
 
 # BGZF random access (include/nxz_engine.h: nxz_bgzf_index / nxz_bgzf_read_ranges)
 RANGE_UOFF, RANGE_VOFF = 0, 1
@@ -140,6 +147,10 @@ def load_library():
         L.nxz_batch_decompress_size.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.nxz_batch_decompress_size_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        L.nxz_deflate_stream_bound.restype = C.c_size_t
+        L.nxz_deflate_stream_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
+        L.nxz_batch_deflate_streams.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -339,6 +350,40 @@ class Engine:
         self._check(rc, "nxz_batch_decompress_size_framed")
         return results, frames
 
+    # ---- one stream per device buffer: buffers of any length, each as one raw / zlib / gzip stream ----
+    def deflate_stream_bound(self, src_len, hist_max=0, fmt=FMT_ZLIB):
+        """nxz_deflate_stream_bound: the dst_cap a buffer of src_len bytes needs"""
+        return self.L.nxz_deflate_stream_bound(src_len, hist_max, fmt)
+
+    def deflate_stream_jobs(self, fc, fmt, jobs, results=None, hist_max=0, level=-1):
+        """nxz_batch_deflate_streams on a HOST array of STREAM_JOB_DTYPE records (device addresses).  Returns (rc, results): rc 0 /
+        -errno, results a uint8 device tensor of len(jobs) STREAM_RESULT_DTYPE records.  Asynchronous on torch's current stream."""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, STREAM_JOB_DTYPE)
+        n = len(jobs)
+        if results is None:
+            results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_deflate_streams(self.ctx, fc, fmt, level, hist_max, jobs.ctypes.data if n else None, n, results.data_ptr(),
+                                              self.stream_handle())
+        return rc, results
+
+    def deflate_streams(self, fc, fmt, bufs, hist_max=0, level=-1):
+        """bufs: uint8 device tensors (16-byte aligned, any length) -> one stream each (FMT_RAW / FMT_ZLIB / FMT_GZIP).  Returns
+        (out, offsets, results): stream i stands at out[offsets[i]:] (a uint8 device tensor with room for every stream's bound),
+        results[i].out_len bytes long; results as deflate_stream_jobs.  Asynchronous: results_to_host(results, STREAM_RESULT_DTYPE)."""
+        t = self.torch
+        j = np.zeros(len(bufs), STREAM_JOB_DTYPE)
+        caps = [self.deflate_stream_bound(b.numel(), hist_max, fmt) for b in bufs]
+        offsets = np.zeros(len(bufs) + 1, np.int64)
+        offsets[1:] = np.cumsum([(c + 15) & ~15 for c in caps])
+        out = t.empty(max(int(offsets[-1]), 1), dtype=t.uint8, device=self.dev)
+        for i, b in enumerate(bufs):
+            assert b.dtype == t.uint8 and b.is_contiguous() and b.device == out.device
+            j[i] = (b.data_ptr() if b.numel() else 0, out.data_ptr() + int(offsets[i]), b.numel(), caps[i])
+        rc, results = self.deflate_stream_jobs(fc, fmt, j, hist_max=hist_max, level=level)
+        self._check(rc, "nxz_batch_deflate_streams")
+        return out, offsets, results
+
     def frames_to_host(self, frames):
         self.torch.cuda.synchronize(self.dev)
         return frames.cpu().numpy().view(FRAME_DTYPE)
@@ -484,6 +529,6 @@ class Engine:
                     "nxz_batch_wrap")
         return results
 
-    def results_to_host(self, results):
+    def results_to_host(self, results, dtype=RESULT_DTYPE):
         self.torch.cuda.synchronize(self.dev)
-        return results.cpu().numpy().view(RESULT_DTYPE)
+        return results.cpu().numpy().view(dtype)
