@@ -417,7 +417,8 @@ typedef struct nxz_batch_frame {
  * take the slower route); resume and hist_len must be 0.  results[i] is what nxz_batch_decompress writes for
  * the job's deflate data alone -- except after a header failure, when it is all zero with cc =
  * NXZ_CC_INVALID_OP and dst is not touched.  Bytes after the trailer are no error: frames[i].end < src_len.
- * A second member inside one job is not decoded. */
+ * A second member inside one job is not decoded (`end` tells where it starts); nxz_batch_gzip_members_size / _decode below
+ * decode every member of a job. */
 int nxz_batch_decompress_framed(nxz_ctx_t *ctx, int fmt, const nxz_batch_job_t *jobs, size_t n,
 				nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
 
@@ -522,6 +523,76 @@ int nxz_batch_decompress_size(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_
 int nxz_batch_decompress_size_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *dict /* may be NULL */,
 				     const nxz_batch_job_t *jobs, size_t n,
 				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Multi-member gzip streams: member index and batch decode
+ * ---------------------------------------------------------------------- */
+/* RFC 1952: a gzip file is a series of members, and a reader decodes all of them (`cat a.gz b.gz`, WARC records, appended logs).
+ * These two calls extend the two-pass recipe to jobs whose src is such a series; the member is the only granule -- no checkpoints
+ * inside a member, no range reads.  The rules (power-gzip_amd/csrc/nxz_gzip_members.h), in the order they are checked:
+ *   1. a job with resume or hist_len set: NXZ_GZS_INVALID, nothing walked;
+ *   2. member 0 is parsed at offset 0 by the gzip parser of the framed calls;
+ *   3. behind an OK member that ends at e: e == src_len -- stop, NXZ_GZS_OK; fewer than 2 bytes left, or the next two are not
+ *      1f 8b -- stop, NXZ_GZS_OK with consumed = e (trailing zeros and trailing garbage are the caller's business, as with
+ *      frames[i].end); otherwise the next member starts at e;
+ *   4. a member that fails (header, FHCRC, truncation, deflate data, ISIZE != the counted size) ends the walk:
+ *      NXZ_GZS_MEMBER_FAILED, failed = its index, its record carries the NXZ_FRAME_* status; the members before it stay valid;
+ *   5. members beyond member_cap are walked and counted (members, out_len, consumed are true values) but not stored:
+ *      NXZ_GZS_MORE_MEMBERS, unless a member failed;
+ *   6. uoff is the running sum of the OK members' sizes.
+ * A failed member's record holds uoff, coff and status, hdr_len when its header was read, and clen, check and the counted isize
+ * when its trailer was read (NXZ_FRAME_BAD_LENGTH); its other fields are 0. */
+typedef struct nxz_gzip_member {   /* DEVICE, 32 bytes; offsets count from the job's src / dst */
+	uint64_t uoff;             /* where the member's output starts in the job's output */
+	uint32_t coff, clen;       /* member start, header + deflate + trailer bytes */
+	uint32_t hdr_len, isize;   /* isize: the size the walk counted (== ISIZE as read when status is OK) */
+	uint32_t check;            /* CRC-32 as read */
+	uint32_t status;           /* NXZ_FRAME_* of this member */
+} nxz_gzip_member_t;
+typedef struct nxz_gzip_stream {   /* DEVICE, 32 bytes, one per job */
+	uint32_t status;           /* NXZ_GZS_* */
+	uint32_t members;          /* members found (may exceed member_cap) */
+	uint32_t failed;           /* index of the first member whose status != NXZ_FRAME_OK (else == members) */
+	uint32_t consumed;         /* bytes of src covered by whole OK members */
+	uint64_t out_len;          /* sum of isize over the OK members (64 bits: may pass 4 GiB in the size call) */
+	uint32_t cc, reserved;     /* raw decoder's code of the failed member (3 when its deflate data was cut short), else 0 */
+} nxz_gzip_stream_t;
+enum { NXZ_GZS_OK = 0, NXZ_GZS_MEMBER_FAILED, NXZ_GZS_MORE_MEMBERS, NXZ_GZS_TARGET_SPACE, NXZ_GZS_INVALID };
+
+/* Pass 1, the member index: one wavefront walks a job member after member inside ONE launch (power-gzip_amd/csrc/
+ * nxz_gzip_members.hip) -- header, the size walk of nxz_batch_decompress_size over the deflate bytes, the 8-byte trailer --
+ * and writes members[i * member_cap + k] for k < min(members found, member_cap) and streams[i].  jobs[].src may have any
+ * alignment; dst and dst_cap are not looked at, nothing but the two arrays is written.  A member of more than 2^32 - 1 bytes
+ * of output is NXZ_FRAME_DEFLATE (cc 13).  One huge job is one wavefront's serial walk: parallelism comes from the batch.
+ * zlib streams are not concatenable and are not handled; no dictionaries.
+ * jobs, members (n * member_cap records) and streams (n) are DEVICE arrays.  Asynchronous on `stream`, no host wait.
+ * Returns 0 (n == 0 included); -EINVAL (ctx, member_cap == 0, n >= 2^31, a NULL array with n > 0); -ENODEV in a forked child. */
+int nxz_batch_gzip_members_size(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+				nxz_gzip_member_t *members /* n * member_cap */, nxz_gzip_stream_t *streams, void *stream);
+
+/* Pass 2, the decode, from the arrays pass 1 wrote (the same member_cap): the first min(streams[i].failed, member_cap) members
+ * of every job -- its stored OK members -- become framed gzip jobs (src + coff, clen bytes, into dst + uoff, isize bytes) in the
+ * stream's scratch and go through the routes of nxz_batch_decompress_framed as ONE batch of at most total_members jobs; then the
+ * decode's verdict is joined back: members[].status takes the frame status (NXZ_FRAME_BAD_CHECK shows here, the size pass cannot
+ * see it), streams[i].out_len becomes the bytes decoded -- the sizes of the members that decoded OK --, and a job with a member
+ * that failed gets NXZ_GZS_MEMBER_FAILED, failed = the first such index and cc = its raw result's code; the other members of the
+ * job are decoded all the same.  A job the decode does not touch at all (dst not written, its streams[i] unchanged but for status):
+ *   NXZ_GZS_TARGET_SPACE   streams[i].out_len > jobs[i].dst_cap;
+ *   NXZ_GZS_INVALID        its summary is none of OK / MEMBER_FAILED / MORE_MEMBERS (refused before: the size pass again); or one of
+ *                          its stored OK records is not OK or points outside the job
+ *                          (coff + clen > src_len, uoff + isize > dst_cap: a stale or foreign index); or total_members is too
+ *                          small for the batch -- then every job from the first that does not fit on.
+ * total_members (HOST) is an upper bound of the members to decode: n * member_cap is always one, sum(min(failed, member_cap))
+ * is the tightest; slots beyond the real count are empty jobs that every route ends at once.  Member outputs land at arbitrary
+ * offsets of the job's target: a member whose dst is not 16-byte aligned takes the stream-per-wavefront route, as BGZF members
+ * of odd sizes do in nxz_batch_unpack_gzip.
+ * Asynchronous on `stream`: no host wait, no allocation once the stream's scratch holds a batch of this size (about 150 bytes a
+ * member).  Returns 0 (n == 0 included); -EINVAL (ctx, member_cap == 0, total_members < n, n >= 2^31, a NULL array with n > 0);
+ * -E2BIG (min(total_members, n * member_cap) >= 2^31); -ENOMEM; -ENODEV in a forked child.
+ * Speed: not measured yet; tools/bench_members.py writes profiles/r12_members.txt. */
+int nxz_batch_gzip_members_decode(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+				  nxz_gzip_member_t *members, nxz_gzip_stream_t *streams,
+				  size_t total_members /* HOST: an upper bound, n * member_cap is always one */, void *stream);
 
 /* ------------------------------------------------------------------------
  * One stream per device buffer: batched deflate of buffers of any length

@@ -715,6 +715,57 @@ extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz
 }
 
 // ---------------------------------------------------------------------------
+// Multi-member gzip jobs (nxz_gzip_members.hip, the rules in nxz_gzip_members.h).  The index is the size query's shape: a wavefront
+// a job, from 128 jobs on the long ones first, the order in this stream's scratch under the lease.  The decode holds frame_use[s]
+// from its first kernel to its last -- BUF_GZIP_MEMBERS is the framed batch framed_locked works on -- and never waits for the host.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_gzip_members_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+					   nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, void *stream)
+{
+	if (!c || member_cap == 0 || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
+	}) : nullptr;
+	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
+	const int rc = nxz_launch_gzip_members_index(jobs, n, member_cap, members, streams, order, s);
+	if (rc) { set_err("gzip members index launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+extern "C" int nxz_batch_gzip_members_decode(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+					     nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, size_t total_members, void *stream)
+{
+	if (!c || member_cap == 0 || total_members < n || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	const uint64_t slots = (uint64_t)n * member_cap;                     // (n < 2^31, member_cap < 2^32: no overflow)
+	const size_t total = (size_t)std::min<uint64_t>(total_members, slots);
+	if (total >= (1u << 31) || slots >= (1ull << 39)) return -E2BIG;     // (the framed batch; a thread a record slot in one grid)
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_GZIP_MEMBERS].grow(s, nxz_gzip_members_workspace(n, total));
+		return sc.buf[BUF_GZIP_MEMBERS].p;
+	});
+	if (!ws) return -ENOMEM;
+	nxz_batch_job_t *xjobs = nullptr;
+	nxz_batch_result_t *xresults = nullptr;
+	nxz_batch_frame_t *xframes = nullptr;
+	int rc = nxz_launch_gzip_members_expand(jobs, n, member_cap, members, streams, total, ws, &xjobs, &xresults, &xframes, s);
+	if (rc) { set_err("gzip members expand launch", (hipError_t)rc); return -EIO; }
+	if ((rc = framed_locked(c, NXZ_FMT_GZIP, xjobs, total, xresults, xframes, s)) != 0) return rc;
+	rc = nxz_launch_gzip_members_join(n, member_cap, members, streams, total, ws, s);
+	if (rc) { set_err("gzip members join launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+// ---------------------------------------------------------------------------
 // One stream per device buffer (nxz_streams.hip, the rules in nxz_streams.h).  The host makes one pass over the streams -- the
 // refusals and the block prefix first[n + 1] -- into pinned staging, uploads it with the descriptors, and queues per chunk of
 // NXZ_STREAMS_CHUNK blocks: expand -> nxz_batch_compress on the device jobs -> layout and checksum joins -> pack; a prologue in

@@ -136,6 +136,17 @@ int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n,
 int nxz_launch_inflate_size(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const uint32_t *order,
 			    uint32_t dict_window, hipStream_t stream);
 int nxz_launch_size_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);   /* nxz_launch_frame_trailer without the checksum comparison */
+/* nxz_gzip_members.hip: multi-member gzip jobs (nxz_gzip_members.h has the rules).  The index: a wavefront a job, member after member
+ * inside the kernel.  The decode: expand (records checked, the plan, the members as framed jobs in ws: nxz_gzip_members_workspace
+ * bytes) -> the framed decode of *xjobs -> join (the verdicts back into members and streams) */
+int nxz_launch_gzip_members_index(const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap, nxz_gzip_member_t *members,
+				  nxz_gzip_stream_t *streams, const uint32_t *order, hipStream_t stream);
+size_t nxz_gzip_members_workspace(size_t n, size_t total_members);
+int nxz_launch_gzip_members_expand(const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap, const nxz_gzip_member_t *members,
+				   nxz_gzip_stream_t *streams, size_t total_members, uint8_t *ws, nxz_batch_job_t **xjobs,
+				   nxz_batch_result_t **xresults, nxz_batch_frame_t **xframes, hipStream_t stream);
+int nxz_launch_gzip_members_join(size_t n, uint32_t member_cap, nxz_gzip_member_t *members, nxz_gzip_stream_t *streams,
+				 size_t total_members, uint8_t *ws, hipStream_t stream);
 /* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
  * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
  * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */

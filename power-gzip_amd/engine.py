@@ -49,6 +49,14 @@ STREAM_RESULT_DTYPE = np.dtype([("cc", "<u4"), ("blocks", "<u4"), ("out_len", "<
                                 ("stored", "<u4"), ("reserved", "<u4")])
 assert STREAM_JOB_DTYPE.itemsize == 32 and STREAM_RESULT_DTYPE.itemsize == 32
 
+# multi-member gzip jobs (include/nxz_engine.h: nxz_batch_gzip_members_size / _decode)
+GZIP_MEMBER_DTYPE = np.dtype([("uoff", "<u8"), ("coff", "<u4"), ("clen", "<u4"), ("hdr_len", "<u4"), ("isize", "<u4"),
+                              ("check", "<u4"), ("status", "<u4")])
+GZIP_STREAM_DTYPE = np.dtype([("status", "<u4"), ("members", "<u4"), ("failed", "<u4"), ("consumed", "<u4"), ("out_len", "<u8"),
+                              ("cc", "<u4"), ("reserved", "<u4")])
+assert GZIP_MEMBER_DTYPE.itemsize == 32 and GZIP_STREAM_DTYPE.itemsize == 32
+GZS_OK, GZS_MEMBER_FAILED, GZS_MORE_MEMBERS, GZS_TARGET_SPACE, GZS_INVALID = range(5)
+
 # BGZF random access (include/nxz_engine.h: nxz_bgzf_index / nxz_bgzf_read_ranges)
 RANGE_UOFF, RANGE_VOFF = 0, 1
 RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED = range(4)
@@ -148,6 +156,9 @@ def load_library():
         L.nxz_batch_decompress_size_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
         L.nxz_deflate_stream_bound.restype = C.c_size_t
+        L.nxz_batch_gzip_members_size.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_gzip_members_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]
         L.nxz_deflate_stream_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
         L.nxz_batch_deflate_streams.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p]
@@ -349,6 +360,27 @@ class Engine:
                                                      results.data_ptr(), frames.data_ptr(), self.stream_handle())
         self._check(rc, "nxz_batch_decompress_size_framed")
         return results, frames
+
+    # ---- multi-member gzip jobs: the member index, then every stored member decoded as one framed batch ----
+    def gzip_members_size(self, jobs, n, member_cap, members=None, streams=None):
+        """nxz_batch_gzip_members_size: jobs whose src is a series of gzip members.  Returns (members, streams), uint8 device
+        tensors of n * member_cap GZIP_MEMBER_DTYPE and n GZIP_STREAM_DTYPE records; dst is not touched."""
+        t = self.torch
+        if members is None:
+            members = t.empty(n * member_cap * GZIP_MEMBER_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if streams is None:
+            streams = t.empty(n * GZIP_STREAM_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        self._check(self.L.nxz_batch_gzip_members_size(self.ctx, jobs.data_ptr(), n, member_cap, members.data_ptr(), streams.data_ptr(),
+                                                       self.stream_handle()), "nxz_batch_gzip_members_size")
+        return members, streams
+
+    def gzip_members_decode(self, jobs, n, member_cap, members, streams, total_members=None):
+        """nxz_batch_gzip_members_decode on what gzip_members_size returned (updated in place).  total_members: an upper bound of
+        the members to decode, n * member_cap when None."""
+        total = n * member_cap if total_members is None else total_members
+        self._check(self.L.nxz_batch_gzip_members_decode(self.ctx, jobs.data_ptr(), n, member_cap, members.data_ptr(), streams.data_ptr(),
+                                                         total, self.stream_handle()), "nxz_batch_gzip_members_decode")
+        return members, streams
 
     # ---- one stream per device buffer: buffers of any length, each as one raw / zlib / gzip stream ----
     def deflate_stream_bound(self, src_len, hist_max=0, fmt=FMT_ZLIB):
