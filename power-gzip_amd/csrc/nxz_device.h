@@ -19,6 +19,10 @@ typedef struct nxz_dht_prepared {
 // two bitmaps over the positions of the block (bit p of the first: a literal token starts at
 // position p; of the second: a match token starts there) and the match tokens in parse order,
 // one dword each: length - 3 | (distance - 1) << 8.
+// Who writes the job's result record: the LZ77 kernel spbc, sfbt (its match count) and zeros in the rest; the entropy
+// kernel, launched behind it on the same jobs and results, cc, tpbc, tebc, sfbt = 0 and crc / adler, which it makes of the
+// source it reads anyway (nxz_cksum_slices.h).  Nothing may read crc / adler between the two launches.  The forms of
+// the LZ77 kernel that finish the block themselves (NXZ_LZ77_FUSED_FHT, NXZ_LZ77_FUSED_GEN) write every field.
 #define NXZ_TOK_LITBITS    0u
 #define NXZ_TOK_MATCHBITS  8192u
 #define NXZ_TOK_RECORDS    16384u

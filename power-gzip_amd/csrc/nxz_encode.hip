@@ -16,11 +16,15 @@
 // codes once each, a round ahead, by the lanes that copy them to LDS; the lanes of the round only
 // load a finished code.  Nothing here is serial over the block, and with ~21 KiB of LDS seven
 // workgroups share a CU, so the latencies of one hide behind the others.
+// The block's checksums are made here as well (the LZ77 kernel's non-fused forms leave crc / adler of the result
+// record to this kernel: its one workgroup a CU has nothing to hide their table look-ups behind): a pass over the
+// source at the top, 64-byte slices side by side (nxz_cksum_slices.h), the CRC table in the not yet used windows.
 // Bit for bit the encoder of oracle/nxz_lz77.c (put_tokens / nxo_encode_fixed / nxo_encode_dynamic).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "nxz_device.h"
+#include "nxz_cksum_slices.h"
 
 namespace nxze {
 
@@ -121,6 +125,8 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 	__shared__ uint16_t rankpre[2048 + 2];                                 // matches in front of every 32 positions; [2048] = all
 	__shared__ uint32_t wsum[2][NT / 64];
 	__shared__ uint32_t errflag;
+	__shared__ uint32_t ckred[4][NT / 64];                                 // the wavefronts' checksum parts
+	__shared__ uint32_t ckout[2];                                          // crc, adler of the result record
 	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 	const uint32_t bid = blockIdx.x;
 	if (bid >= njobs) return;
@@ -181,6 +187,33 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 			}
 		}
 	};
+	// ---- CRC-32 and Adler-32 of the source (seeded: job.in_crc, job.in_adler), as the LZ77 kernel's fused forms make them ----
+	// The slice-by-4 table (4 KiB) stands in the windows, which are cleared only afterwards: no LDS of its own, seven
+	// workgroups a CU as before.
+	{
+		static_assert(sizeof(win) >= 1024 * sizeof(uint32_t) && NT == (int)nxzck::LANES, "the CRC table borrows the windows; a lane per table column");
+		uint32_t *T = &win[0][0];
+		nxzck::table_column(T, (uint32_t)t);
+		__syncthreads();
+		const nxzck::Shape shp = nxzck::shape_of(n);
+		const nxzck::Part p = nxzck::lane_part((const uint8_t *)src, shp, job.in_crc ^ 0xffffffffu, (uint32_t)t, T);
+		uint32_t c = p.crc, tc = p.tailcrc, a1 = p.s1, a2 = p.s2;
+		for (int o = 32; o > 0; o >>= 1) {
+			c ^= __shfl_down(c, o, 64);
+			tc ^= __shfl_down(tc, o, 64);
+			a1 += __shfl_down(a1, o, 64);
+			a2 += __shfl_down(a2, o, 64);
+		}
+		if (lane == 0) { ckred[0][wave] = c; ckred[1][wave] = tc; ckred[2][wave] = a1; ckred[3][wave] = a2; }
+		__syncthreads();                                         // (and the table is done with: the windows are cleared below)
+		if (t == 0) {
+			c = 0; tc = 0; a1 = 0; a2 = 0;
+			for (int w = 0; w < NT / 64; w++) { c ^= ckred[0][w]; tc ^= ckred[1][w]; a1 += ckred[2][w]; a2 += ckred[3][w]; }
+			uint32_t oc, oa;
+			nxzck::finish(shp, job.in_crc, job.in_adler, c, tc, a1, a2, oc, oa);
+			ckout[0] = oc; ckout[1] = oa;                        // (thread 0 reads them back itself, at the end)
+		}
+	}
 	Fetch nx;
 	fetch(0, nx);                                                // round 0's bytes travel while the tables are set up
 
@@ -328,6 +361,8 @@ __global__ __launch_bounds__(NT) void encode_kernel(const nxz_batch_job_t *__res
 		r->tpbc = cc == NXZ_CC_TARGET_SPACE ? 0 : tpbc;
 		r->tebc = (uint32_t)(totbits & 7);
 		r->sfbt = 0;                                            // (the LZ77 kernel left its match count there)
+		r->crc = ckout[0];
+		r->adler = ckout[1];
 	}
 }
 

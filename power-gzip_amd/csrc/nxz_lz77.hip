@@ -12,12 +12,13 @@
 // (nxz_device.h, NXZ_TOK_*): a bitmap of the positions where a literal token starts, a bitmap of
 // the positions where a match token starts, the (length, distance) records of the matches in
 // parse order, the LZ symbol counts (286 + 30, the COUNT function codes' out_lzcount and the
-// input of the table generator nxz_dhtgen.hip) and the checksums.  The entropy stage
-// (nxz_encode.hip) makes the deflate block from them.
+// input of the table generator nxz_dhtgen.hip).  The entropy stage (nxz_encode.hip) makes the deflate block from
+// them, and the block's checksums from the source: only the forms of this kernel that finish the block themselves
+// (FUSED, GEN -- no entropy launch behind them) have the cksum phase.
 //
 // Phases per sub-block (the block stays in LDS from load to the last tile):
 //   load     coalesced 16 B/lane global loads of [window|block] into LDS
-//   cksum    CRC-32 (64-byte slices, slice-by-4, GF(2) weights, XOR reduce) and Adler-32 (v_dot4)
+//   cksum    (FUSED / GEN only) CRC-32 (64-byte slices, slice-by-4, GF(2) weights, XOR reduce) and Adler-32 (v_dot4)
 //   seed     window positions -> head[] by LDS atomicMax (order free)
 //   per 16 KiB tile:
 //     hash   four positions per lane: 4-byte hash -> slot offsets, transposed per 512-position
@@ -43,6 +44,7 @@
 #include "nxz_device.h"
 #include "nxz_dhtgen_dev.h"
 #include "nxz_dict.h"
+#include "nxz_cksum_slices.h"
 
 // Diagnostic only (tools/phase_profile.py, a build with -DNXZ_LZ77_PROF: tools/build_variant.sh prof nxz_lz77.hip -DNXZ_LZ77_PROF):
 // per-phase cycle sums of every workgroup's thread 0.  Compiled out of the product: the counters cost a dozen
@@ -110,7 +112,7 @@ constexpr uint32_t OFF_SBITS = OFF_MLEN + PTILE;         // 512 x u32   (aliased
 constexpr uint32_t OFF_MBITS = OFF_SBITS + PTILE / 8;    // 512 x u32   (aliased: JUMP u16[1024]; literal-token bitmap of the final walk)
 constexpr uint32_t OFF_X     = OFF_MBITS + PTILE / 8;    // 1024 x u16
 constexpr uint32_t OFF_ENTRY = OFF_X + NSEG * 2;         // 1024 x u16
-constexpr uint32_t OFF_BITS  = OFF_ENTRY + NSEG * 2;     // the CRC tables (4 KiB) before the first tile, match-phase queues later
+constexpr uint32_t OFF_BITS  = OFF_ENTRY + NSEG * 2;     // the CRC tables (4 KiB, the forms with a cksum phase) before the first tile, match-phase queues later
 // The match phase's queues, per wave: LQ_CAP long positions (a batch goes to level 1 of M2 when LQ_MIN are waiting: a unit adds
 // up to 64 at a time) and XQ_CAP positions that are still open after OPEN2 bytes (level 2 when XQ_MIN are waiting).  The
 // fuller a batch, the fewer trips: with 96 / 32 and 80 / 16 (round 4) level 1 ran 70 % full and level 2 with 16 lanes of 64.
@@ -171,52 +173,10 @@ __device__ __forceinline__ uint32_t equal16(const uint32_t *inw, uint32_t a, uin
 	return n;
 }
 
-// GF(2)[x] multiply modulo the reflected CRC-32 polynomial
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b)
-{
-	uint32_t r = 0;
-#pragma unroll 8
-	for (int i = 0; i < 32; i++) {
-		r ^= (b & 0x80000000u) ? a : 0;
-		a = (a >> 1) ^ ((a & 1) ? 0xedb88320u : 0);
-		b <<= 1;
-	}
-	return r;
-}
-
-// x^(8*64*k) mod P for k = 0..1023 (compile-time): what a 64-byte slice that is followed by k
-// more slices has to be multiplied with.
-constexpr uint32_t cgf_mul(uint32_t a, uint32_t b)
-{
-	uint32_t r = 0;
-	for (int i = 0; i < 32; i++) {
-		if (b & 0x80000000u) r ^= a;
-		a = (a >> 1) ^ ((a & 1) ? 0xedb88320u : 0);
-		b <<= 1;
-	}
-	return r;
-}
-struct PowTab { uint32_t v[1024]; };
-constexpr PowTab make_pow()
-{
-	PowTab p{};
-	uint32_t m = 0x00800000u;                 // x^8
-	for (int k = 0; k < 6; k++) m = cgf_mul(m, m);   // x^512
-	p.v[0] = 0x80000000u;
-	for (int i = 1; i < 1024; i++) p.v[i] = cgf_mul(p.v[i - 1], m);
-	return p;
-}
-__device__ const PowTab CRC_POW = make_pow();
-// x^(8 r) mod P for r = 0..64
-struct Pow8Tab { uint32_t v[65]; };
-constexpr Pow8Tab make_pow8()
-{
-	Pow8Tab p{};
-	p.v[0] = 0x80000000u;
-	for (int i = 1; i <= 64; i++) p.v[i] = cgf_mul(p.v[i - 1], 0x00800000u);
-	return p;
-}
-__device__ const Pow8Tab CRC_POW8 = make_pow8();
+// GF(2)[x] multiply modulo the reflected CRC-32 polynomial and the slices' weights x^(512 k), x^(8 r): nxz_cksum_slices.h
+using nxzck::gf_mul;
+using nxzck::CRC_POW;
+using nxzck::CRC_POW8;
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
 {
@@ -637,6 +597,10 @@ __device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jo
 	uint32_t *scan = (uint32_t *)(lds + OFF_SCAN);
 	uint32_t *hist = (uint32_t *)(lds + OFF_HIST);
 	uint32_t *misc = (uint32_t *)(lds + OFF_MISC);
+	// The forms that finish the block themselves make its checksums too.  The others hand tokens to the entropy kernel, which
+	// reads the source anyway and has six more workgroups on its CU to hide the table look-ups behind: no cksum phase here, no
+	// CRC table in LDS, and crc / adler of the result record are that kernel's to write.
+	constexpr bool CKSUM = FUSED || GEN;
 #ifdef NXZ_LZ77_PROF
 	uint32_t *profacc = (uint32_t *)(lds + OFF_PROF);
 #endif
@@ -671,8 +635,8 @@ __device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jo
 	const NXZ_GLOBAL uint8_t *src = (const NXZ_GLOBAL uint8_t *)job.src;
 	// CRC weights (constant memory), fetched up front so that their latency hides behind the load phase
 	const uint32_t K1 = n ? (end - 1) >> 6 : 0;              // 64-byte slice (LDS aligned) that holds the last byte
-	const uint32_t pw_slice = CRC_POW.v[(1022 - t) & 1023];  // x^(512 (1022 - t))
-	const uint32_t pw_tail = CRC_POW8.v[n ? end - K1 * 64 : 0]; // x^(8 r), r = bytes of the last slice (an empty block has none)
+	const uint32_t pw_slice = CKSUM ? CRC_POW.v[(1022 - t) & 1023] : 0;  // x^(512 (1022 - t))
+	const uint32_t pw_tail = CKSUM ? CRC_POW8.v[n ? end - K1 * 64 : 0] : 0; // x^(8 r), r = bytes of the last slice (an empty block has none)
 
 	// ---------------- load ----------------
 	{
@@ -700,7 +664,7 @@ __device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jo
 	if (t < 20) profacc[t] = 0;
 #endif
 	// slice-by-4 CRC tables live in the (not yet used) bit buffer: T[k][i] = i advanced by k+1 zero bytes
-	{
+	if constexpr (CKSUM) {
 		uint32_t c = t & 255;
 		for (int k = 0; k < 8 * ((t >> 8) + 1); k++) c = (c >> 1) ^ ((c & 1) ? 0xedb88320u : 0);
 		bitbuf[t] = c;
@@ -717,8 +681,9 @@ __device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jo
 	// x^(512 j) * x^(8 r): the first factor is applied per thread, the XOR reduce is linear, so the
 	// second is applied once to the reduced value before the tail slice's CRC joins.  in_crc is
 	// XORed into the state in front of the first data byte (history length is a multiple of 16).
-	uint32_t out_crc, out_adler;
-	{
+	// (!CKSUM: the entropy kernel makes them, nxz_encode.hip -- PROF slot 1 stays and reads about 0)
+	uint32_t out_crc = 0, out_adler = 0;
+	if constexpr (CKSUM) {
 		uint32_t *T = bitbuf;                                   // T[k*256 + i], k = 0..3
 		const uint32_t initx = job.in_crc ^ 0xffffffffu;
 		const int sidx = (int)t - 1023 + (int)K1;               // my slice
@@ -1852,7 +1817,8 @@ __device__ __forceinline__ void lz77_body(const nxz_batch_job_t *__restrict__ jo
 		PROF(9);
 	}
 
-	// ---------------- result: checksums and counts (the entropy stage adds cc, tpbc, tebc) ----------------
+	// ---------------- result: counts, and with the block finished here (CKSUM) the checksums; otherwise the entropy stage
+	// adds crc, adler, cc, tpbc, tebc ----------------
 	if (t == 0) {
 		nxz_batch_result_t r;
 		r.cc = 0; r.tpbc = 0; r.tebc = 0;
