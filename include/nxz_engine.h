@@ -528,8 +528,8 @@ int nxz_batch_decompress_size_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *
  * Multi-member gzip streams: member index and batch decode
  * ---------------------------------------------------------------------- */
 /* RFC 1952: a gzip file is a series of members, and a reader decodes all of them (`cat a.gz b.gz`, WARC records, appended logs).
- * These two calls extend the two-pass recipe to jobs whose src is such a series; the member is the only granule -- no checkpoints
- * inside a member, no range reads.  The rules (power-gzip_amd/csrc/nxz_gzip_members.h), in the order they are checked:
+ * These two calls extend the two-pass recipe to jobs whose src is such a series; the member is the only granule here (checkpoints
+ * inside a member and range reads: nxz_batch_checkpoint_index / nxz_checkpoint_read_ranges below).  The rules (power-gzip_amd/csrc/nxz_gzip_members.h), in the order they are checked:
  *   1. a job with resume or hist_len set: NXZ_GZS_INVALID, nothing walked;
  *   2. member 0 is parsed at offset 0 by the gzip parser of the framed calls;
  *   3. behind an OK member that ends at e: e == src_len -- stop, NXZ_GZS_OK; fewer than 2 bytes left, or the next two are not
@@ -685,6 +685,76 @@ int nxz_bgzf_read_ranges(nxz_ctx_t *ctx, const uint8_t *packed, uint64_t packed_
 			 int kind, const nxz_bgzf_range_t *ranges, size_t n,
 			 uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,
 			 uint64_t *out_len, uint64_t *decoded, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Checkpoints: an index into raw, zlib and gzip streams, and range reads through it
+ * ---------------------------------------------------------------------- */
+/* What the BGZF calls do for images cut into members, for any deflate stream: byte ranges out of the middle of a stream without
+ * inflating what lies in front.  A checkpoint is a BLOCK HEADER of the deflate data: the bit of the job's src where the header
+ * starts (framing included) and the bytes of output in front of it.  Checkpoints stand only at block headers -- a stream whose
+ * blocks are huge has coarse segments.  The rules (power-gzip_amd/csrc/nxz_checkpoint.h):
+ *   1. checkpoint 0 is the first block header: bit = 8 * the framing's header bytes, uoff = 0;
+ *   2. a later header with u bytes of output in front of it is a checkpoint when u - (uoff of the last checkpoint) >= span;
+ *   3. entry [count] is the sentinel: the bit behind the final end-of-block code, and out_len;
+ *   4. segment k is checkpoint k up to entry k + 1: source bytes [cbit[k] >> 3, (cbit[k+1] + 7) >> 3), of the first of them the
+ *      upper (8 - (cbit[k] & 7)) & 7 bits when cbit[k] stands inside a byte, a window of min(uoff[k], 32768) bytes,
+ *      uoff[k+1] - uoff[k] bytes of output;
+ *   5. an index is valid when uoff[0] == 0, cbit and uoff strictly increase over the checkpoints (the sentinel's uoff may equal the
+ *      last checkpoint's: an empty final block), cbit[count] <= 8 * src_len, and every segment's window + source bytes and output
+ *      fit 32 bits. */
+enum { NXZ_CPS_OK = 0, NXZ_CPS_STREAM_FAILED, NXZ_CPS_MORE, NXZ_CPS_NO_OUTPUT, NXZ_CPS_INVALID };
+typedef struct nxz_checkpoint_stream {   /* DEVICE, 32 bytes, one per job */
+	uint32_t status, count;          /* NXZ_CPS_*; count: checkpoints found, may exceed cp_cap (0 for a stream that failed) */
+	uint32_t format, hdr_len;        /* what the framing turned out to be: NXZ_FMT_RAW / _ZLIB / _GZIP, its header bytes */
+	uint64_t out_len;                /* bytes the stream makes */
+	uint32_t cc, frame_status;       /* why a failed stream failed: the raw decoder's code, NXZ_FRAME_* */
+} nxz_checkpoint_stream_t;
+
+/* The index build: one wavefront walks one job in ONE launch (power-gzip_amd/csrc/nxz_checkpoint.hip) -- the header by the parser
+ * of the framed calls (fmt: NXZ_FMT_RAW, _ZLIB, _GZIP, _AUTO; raw has none), then the size walk of nxz_batch_decompress_size, which
+ * reports every block header -- and writes cbit[i * (cp_cap + 1) + k] / uoff[...] for k < min(count, cp_cap), the sentinel at
+ * [count] when count <= cp_cap, and streams[i].  Checkpoints beyond cp_cap are counted, not stored: NXZ_CPS_MORE with the true
+ * count and no sentinel.  Of a gzip job the FIRST member is indexed (several members: jobs cut where nxz_batch_gzip_members_size
+ * says).  A job with resume or hist_len set: NXZ_CPS_INVALID, nothing walked.  A stream that fails or does not reach the end of its
+ * final block: NXZ_CPS_STREAM_FAILED with cc / frame_status, count = 0, its entries are not to be used.  The trailer's checksum is
+ * not checked, as in the size calls.  A stream of more than 2^32 - 1 bytes of output fails with cc 13.
+ * windows (DEVICE, n * cp_cap slots of 32768 bytes, or NULL): the window of every stored checkpoint k of job i -- the
+ * min(uoff[k], 32768) bytes in front of uoff[k] -- copied to the START of slot i * cp_cap + k from jobs[i].dst, which must hold the
+ * stream's decoded output (the caller has just made it with nxz_batch_decompress_framed: the index is the by-product of a decode
+ * already done).  dst == NULL or dst_cap < out_len: NXZ_CPS_NO_OUTPUT, the positions are valid, that stream's windows are not
+ * written.  With windows == NULL dst is never looked at.  Building windows without the full output is not part of this call.
+ * jobs, cbit, uoff, windows and streams are DEVICE arrays.  Asynchronous on `stream`: no host wait, no allocation beyond the
+ * stream's scratch.  Returns 0 (n == 0 included); -EINVAL (ctx, fmt, span == 0, cp_cap == 0, n >= 2^31, a NULL array with n > 0);
+ * -ENODEV in a forked child.
+ * Speed: not measured yet; tools/bench_checkpoints.py writes profiles/r14_checkpoints.txt. */
+int nxz_batch_checkpoint_index(nxz_ctx_t *ctx, int fmt /* RAW, ZLIB, GZIP, AUTO */, const nxz_batch_job_t *jobs, size_t n,
+			       uint64_t span, uint32_t cp_cap,
+			       uint64_t *cbit, uint64_t *uoff,   /* DEVICE, n * (cp_cap + 1) each */
+			       uint8_t *windows,                 /* DEVICE, n * cp_cap * 32768, or NULL */
+			       nxz_checkpoint_stream_t *streams, void *stream);
+
+/* Reads n ranges of ONE stream through its index: the counterpart of nxz_bgzf_read_ranges, with segments for members.  src
+ * (DEVICE, src_len bytes) is the job's src, framing included; cbit / uoff (DEVICE, nidx = count + 1 entries) and windows (DEVICE,
+ * count slots of 32768 bytes; may be NULL for an index of one segment) are one job's part of what nxz_batch_checkpoint_index
+ * wrote.  ranges (DEVICE, n) are uncompressed offsets [begin, end) -- only NXZ_RANGE_UOFF exists here --, mapped onto segments by
+ * the rule of the BGZF call; empty ranges, begin > end, end > out_len, offsets, status, dst_cap, *out_len and -E2BIG behave
+ * exactly as there.  Every segment is decoded at most once per call, however many ranges touch it: [window][source bytes] is
+ * staged into a 16-byte aligned slot of per-stream scratch and goes through nxz_batch_decompress as a job with hist_len = the
+ * window and resume = in_subc << 20, into a slot of exactly the segment's output, in chunks of at most NXZ_BGZF_CHUNK segments
+ * and 1 GiB; a larger segment goes alone.  A segment is good when the decoder made exactly its output and ended with CC 0 or
+ * CC 3 (it runs out of source in front of the next header); a range that touches a segment that is not good is
+ * NXZ_RANGE_DAMAGED and reads as zeros, the other ranges are unaffected.
+ * Before anything is decoded the device checks the index against rule 5: a stale or foreign index never makes a kernel read
+ * outside src or a window slot.  Synchronous.
+ * Returns 0; -EILSEQ: the index is not valid (nothing written); -E2BIG; -EINVAL; -ENOMEM; -ENODEV in a forked child.
+ * *out_len = bytes of all ranges, *decoded = segments inflated (either may be NULL).
+ * Speed: not measured yet (segments go a stream per wavefront: the workgroup kernel hands back jobs with history);
+ * tools/bench_checkpoints.py writes profiles/r14_checkpoints.txt. */
+int nxz_checkpoint_read_ranges(nxz_ctx_t *ctx, const uint8_t *src, uint64_t src_len,
+			       const uint64_t *cbit, const uint64_t *uoff, const uint8_t *windows, uint64_t nidx /* count + 1 */,
+			       const nxz_bgzf_range_t *ranges, size_t n,          /* uncompressed offsets, [begin, end) */
+			       uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,   /* NXZ_RANGE_* */
+			       uint64_t *out_len, uint64_t *decoded, void *stream);
 
 /* Device memory, pinned host memory, streams and asynchronous copies, for callers that hold
  * host buffers and do not link the HIP runtime themselves.  A stream made here is passed as

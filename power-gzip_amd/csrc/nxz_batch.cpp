@@ -1020,3 +1020,96 @@ extern "C" int nxz_bgzf_read_ranges(nxz_ctx_t *c, const uint8_t *packed, uint64_
 	if (decoded) *decoded = needed;
 	return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Checkpoints (nxz_checkpoint.hip, the rules in nxz_checkpoint.h).  The index is the size query's shape: a wavefront a job, from 128
+// jobs on the long ones first, the order in this stream's scratch under the lease; the windows' copies go behind it on `s`, and
+// nothing waits for the host.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_checkpoint_index(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
+					  uint64_t *cbit, uint64_t *uoff, uint8_t *windows, nxz_checkpoint_stream_t *streams, void *stream)
+{
+	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || span == 0 || cp_cap == 0 || n >= (1u << 31) || (n && (!jobs || !cbit || !uoff || !streams)))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
+	}) : nullptr;
+	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
+	const int rc = nxz_launch_checkpoint_index(fmt, jobs, n, span, cp_cap, cbit, uoff, windows, streams, order, s);
+	if (rc) { set_err("checkpoint index launch", (hipError_t)rc); return -EIO; }
+	return 0;
+}
+
+// Ranges of one stream through its checkpoint index: nxz_bgzf_read_ranges with segments for members.  The map (the index check of
+// nxz_checkpoint.hip inside nxz_bgzf.hip's) and ONE wait for its totals, then per chunk of needed segments their inputs staged,
+// nxz_batch_decompress on them, the verdicts and nxz_bgzf.hip's gather, then the zeros of damaged ranges and a last wait.
+// BUF_RNG and BUF_RNG_SLOTS are the BGZF call's: both calls hold frame_use[s] from the first kernel to the last wait.
+extern "C" int nxz_checkpoint_read_ranges(nxz_ctx_t *c, const uint8_t *src, uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff,
+					  const uint8_t *windows, uint64_t nidx, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst,
+					  uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !src || !cbit || !uoff || !offsets || nidx < 2 || nidx > 0xffffffffull || (!windows && nidx > 2) || (n && (!ranges || !status)) ||
+	    n >= (1ull << 31))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t L = nidx - 1;
+	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_RNG].grow(s, nxz_bgzf_ranges_workspace(n, L));
+		return sc.buf[BUF_RNG].p;
+	});
+	if (!ws) return -ENOMEM;
+	int rc = nxz_launch_range_map_clear(ws, n, L, s);
+	if (!rc) rc = nxz_launch_checkpoint_check(src_len, cbit, uoff, L, ws, s);
+	if (!rc) rc = nxz_launch_range_map_ranges(uoff, L, ranges, n, offsets, status, ws, s);
+	if (!rc) rc = nxz_launch_checkpoint_inmax(cbit, uoff, n, L, ws, s);
+	if (rc) { set_err("checkpoint map launch", (hipError_t)rc); return -EIO; }
+	uint64_t ctl[6];
+	HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (ctl[0]) return -EILSEQ;
+	if (out_len) *out_len = ctl[2];
+	if (ctl[2] > dst_cap || (ctl[2] && !dst)) return -E2BIG;
+	const uint64_t needed = ctl[1], pieces = ctl[3];
+	if (!needed) return 0;
+	// an input and an output slot per segment of the chunk, all of the largest needed segment's size: at most 1 GiB of either (a
+	// segment larger than that goes alone)
+	const uint64_t ostride = (std::max<uint64_t>(ctl[4], 16) + 15) & ~(uint64_t)15, istride = (std::max<uint64_t>(ctl[5], 16) + 15) & ~(uint64_t)15;
+	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / std::max(istride, ostride))));
+	const size_t ib = (per * istride + 255) & ~(size_t)255, ob = (per * ostride + 255) & ~(size_t)255,
+		     jb = (per * sizeof(nxz_batch_job_t) + 255) & ~(size_t)255, fb = (per * sizeof(nxz_batch_frame_t) + 255) & ~(size_t)255;
+	uint8_t *const slots = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_RNG_SLOTS].grow(s, ib + ob + jb + fb + per * sizeof(nxz_batch_result_t));
+		return sc.buf[BUF_RNG_SLOTS].p;
+	});
+	if (!slots) return -ENOMEM;
+	uint8_t *const oslots = slots + ib;
+	nxz_batch_job_t *jobs = (nxz_batch_job_t *)(slots + ib + ob);
+	nxz_batch_frame_t *frames = (nxz_batch_frame_t *)(slots + ib + ob + jb);
+	nxz_batch_result_t *results = (nxz_batch_result_t *)(slots + ib + ob + jb + fb);
+	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
+		const uint64_t cnt = std::min(per, needed - k0);
+		rc = nxz_launch_checkpoint_stage(src, cbit, uoff, windows, n, L, ws, k0, cnt, slots, istride, oslots, ostride, jobs, s);
+		if (rc) { set_err("checkpoint stage launch", (hipError_t)rc); return -EIO; }
+		rc = batch_decompress(c, jobs, (size_t)cnt, results, nullptr, s, 0);
+		if (rc) return rc;
+		rc = nxz_launch_checkpoint_verdict(uoff, n, L, ws, k0, cnt, results, frames, s);
+		if (rc) { set_err("checkpoint verdict launch", (hipError_t)rc); return -EIO; }
+		rc = nxz_launch_bgzf_gather(uoff, n, L, pieces, ws, offsets, oslots, ostride, k0, cnt, frames, results, dst, status, s);
+		if (rc) { set_err("checkpoint gather launch", (hipError_t)rc); return -EIO; }
+	}
+	rc = nxz_launch_bgzf_zero(n, offsets, status, dst, s);
+	if (rc) { set_err("checkpoint zero launch", (hipError_t)rc); return -EIO; }
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (decoded) *decoded = needed;
+	return 0;
+}

@@ -230,20 +230,47 @@ extern "C" size_t nxz_bgzf_ranges_workspace(uint64_t n, uint64_t L)
 	return up256(64) + 4 * up256(n * 8) + up256((n + 1) * 8) + up256((L + 1) * 4) + 2 * up256(L * 4 + 4);
 }
 
+// The map in two steps, for a caller that checks an index of its own kind between them (nxz_checkpoint.hip): _clear zeroes ctl and
+// the difference array; the caller's check sets ctl[0] = ws[0] when its index is faulty; _ranges maps ranges in uncompressed
+// offsets (no coff), scans the members (here: the caller's segments) and the ranges.
+extern "C" int nxz_launch_range_map_clear(uint8_t *ws, uint64_t n, uint64_t L, hipStream_t stream)
+{
+	const RangeWs w = range_ws(ws, n, L);
+	(void)hipMemsetAsync(w.ctl, 0, 8 * 8, stream);
+	(void)hipMemsetAsync(w.diff, 0, (L + 1) * 4, stream);
+	return (int)hipGetLastError();
+}
+static void range_map_steps(const uint64_t *coff, const uint64_t *uoff, uint64_t L, int kind, const nxz_bgzf_range_t *ranges, uint64_t n,
+			    uint64_t *offsets, uint32_t *status, const RangeWs &w, hipStream_t stream)
+{
+	if (n)
+		hipLaunchKernelGGL(nxzr::range_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, coff, uoff, L, kind, ranges, n, w.ctl,
+				   status, w.rb, w.rfirst, w.rlen, w.rpieces, w.diff);
+	if (L) hipLaunchKernelGGL(nxzr::member_scan_kernel, dim3(1), dim3(1024), 0, stream, w.diff, uoff, L, w.ctl, w.midx, w.list);
+	hipLaunchKernelGGL(nxzr::range_scan_kernel, dim3(1), dim3(1024), 0, stream, w.rlen, w.rpieces, n, w.ctl, offsets, w.poff);
+}
+extern "C" int nxz_launch_range_map_ranges(const uint64_t *uoff, uint64_t L, const nxz_bgzf_range_t *ranges, uint64_t n, uint64_t *offsets,
+					   uint32_t *status, uint8_t *ws, hipStream_t stream)
+{
+	range_map_steps(uoff, uoff, L, NXZ_RANGE_UOFF, ranges, n, offsets, status, range_ws(ws, n, L), stream);
+	return (int)hipGetLastError();
+}
+// midx[j]: the place of member j among the needed ones (~0: not needed); list[k]: the k-th needed member
+extern "C" void nxz_range_map_lists(uint8_t *ws, uint64_t n, uint64_t L, const uint32_t **midx, const uint32_t **list)
+{
+	const RangeWs w = range_ws(ws, n, L);
+	*midx = w.midx; *list = w.list;
+}
+
 // The map: ws[0..4] (uint64, device) = faulty index, needed members, bytes of all ranges, pieces, largest needed member.
 // L = nidx - 1 members; status / offsets written unless the index is faulty.
 extern "C" int nxz_launch_bgzf_map(const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff, uint64_t L, int kind,
 				   const nxz_bgzf_range_t *ranges, uint64_t n, uint64_t *offsets, uint32_t *status, uint8_t *ws, hipStream_t stream)
 {
 	const RangeWs w = range_ws(ws, n, L);
-	(void)hipMemsetAsync(w.ctl, 0, 8 * 8, stream);
-	(void)hipMemsetAsync(w.diff, 0, (L + 1) * 4, stream);
+	(void)nxz_launch_range_map_clear(ws, n, L, stream);
 	if (L) hipLaunchKernelGGL(nxzr::index_check_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, packed, packed_len, coff, uoff, L, w.ctl);
-	if (n)
-		hipLaunchKernelGGL(nxzr::range_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, coff, uoff, L, kind, ranges, n, w.ctl,
-				   status, w.rb, w.rfirst, w.rlen, w.rpieces, w.diff);
-	if (L) hipLaunchKernelGGL(nxzr::member_scan_kernel, dim3(1), dim3(1024), 0, stream, w.diff, uoff, L, w.ctl, w.midx, w.list);
-	hipLaunchKernelGGL(nxzr::range_scan_kernel, dim3(1), dim3(1024), 0, stream, w.rlen, w.rpieces, n, w.ctl, offsets, w.poff);
+	range_map_steps(coff, uoff, L, kind, ranges, n, offsets, status, w, stream);
 	return (int)hipGetLastError();
 }
 

@@ -108,6 +108,11 @@ int nxz_launch_bgzf_coff(const uint8_t *packed, uint64_t len, uint8_t *ws, uint6
 size_t nxz_bgzf_ranges_workspace(uint64_t n, uint64_t L);
 int nxz_launch_bgzf_map(const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff, uint64_t L, int kind,
 			const nxz_bgzf_range_t *ranges, uint64_t n, uint64_t *offsets, uint32_t *status, uint8_t *ws, hipStream_t stream);
+/* the map in steps, for an index of another kind (nxz_checkpoint.hip): clear, the caller's own check (ws[0] != 0: faulty), the ranges */
+int nxz_launch_range_map_clear(uint8_t *ws, uint64_t n, uint64_t L, hipStream_t stream);
+int nxz_launch_range_map_ranges(const uint64_t *uoff, uint64_t L, const nxz_bgzf_range_t *ranges, uint64_t n, uint64_t *offsets,
+				uint32_t *status, uint8_t *ws, hipStream_t stream);
+void nxz_range_map_lists(uint8_t *ws, uint64_t n, uint64_t L, const uint32_t **midx, const uint32_t **list);
 int nxz_launch_bgzf_jobs(const uint8_t *packed, const uint64_t *coff, const uint64_t *uoff, uint64_t n, uint64_t L, uint8_t *ws,
 			 uint64_t k0, uint64_t cnt, uint8_t *slots, uint64_t stride, nxz_batch_job_t *jobs, hipStream_t stream);
 int nxz_launch_bgzf_gather(const uint64_t *uoff, uint64_t n, uint64_t L, uint64_t pieces, uint8_t *ws, const uint64_t *offsets,
@@ -151,6 +156,20 @@ int nxz_launch_gzip_members_expand(const nxz_batch_job_t *jobs, size_t n, uint32
 				   nxz_batch_result_t **xresults, nxz_batch_frame_t **xframes, hipStream_t stream);
 int nxz_launch_gzip_members_join(size_t n, uint32_t member_cap, nxz_gzip_member_t *members, nxz_gzip_stream_t *streams,
 				 size_t total_members, uint8_t *ws, hipStream_t stream);
+/* nxz_checkpoint.hip: the checkpoint index of raw, zlib and gzip streams and range reads through it (nxz_checkpoint.h has the rules).
+ * The index: a wavefront a job; the windows: a second launch over the stored checkpoints.  The range read's steps around
+ * nxz_batch_decompress: check (ws[0]: index faulty, ws[5]: the largest [window][source] of a needed segment), stage (the jobs of
+ * needed segments k0 .. k0 + cnt - 1, their inputs in islots, their outputs in oslots), verdict (frames[k].status: NXZ_FRAME_OK
+ * for a good segment -- what nxz_launch_bgzf_gather looks at) */
+int nxz_launch_checkpoint_index(int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+				uint8_t *windows, nxz_checkpoint_stream_t *streams, const uint32_t *order, hipStream_t stream);
+int nxz_launch_checkpoint_check(uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff, uint64_t L, uint8_t *ws, hipStream_t stream);
+int nxz_launch_checkpoint_inmax(const uint64_t *cbit, const uint64_t *uoff, uint64_t n, uint64_t L, uint8_t *ws, hipStream_t stream);
+int nxz_launch_checkpoint_stage(const uint8_t *src, const uint64_t *cbit, const uint64_t *uoff, const uint8_t *windows, uint64_t n, uint64_t L,
+				uint8_t *ws, uint64_t k0, uint64_t cnt, uint8_t *islots, uint64_t istride, uint8_t *oslots, uint64_t ostride,
+				nxz_batch_job_t *jobs, hipStream_t stream);
+int nxz_launch_checkpoint_verdict(const uint64_t *uoff, uint64_t n, uint64_t L, uint8_t *ws, uint64_t k0, uint64_t cnt,
+				  const nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);
 /* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
  * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
  * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */

@@ -49,11 +49,16 @@ __device__ __forceinline__ void chain_by_lane(int lane, const uint32_t tl, uint6
 	}
 }
 
+// what the walk calls at every block header -- the bit of src the header starts at, the bytes of output in front of it (the same in
+// every lane) -- unless the caller passes a hook of its own (nxz_checkpoint.hip): nothing
+struct NoHook { __device__ __forceinline__ void operator()(uint64_t, uint32_t) const {} };
+
 // The walk over srclen bytes at src for a target of cap bytes (0xffffffff: no limit); hist: how far a distance may reach in front of
 // the output.  stop says where and why it ended (nxz_size.h; produced and, behind the final end-of-block code, subc are set), end_bit
 // the bit of src it stands at -- in 64 bits, where stop.subc is a 32-bit field.  Every lane gets the same answers.
+template <class Hook = NoHook>
 __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src, const uint32_t srclen, const uint32_t cap, const uint32_t hist,
-				     const int lane, nxz_size_stop_t &stop, uint64_t &end_bit)
+				     const int lane, nxz_size_stop_t &stop, uint64_t &end_bit, Hook hook = Hook())
 {
 	Bits b;
 	b.src = src; b.srclen = srclen; b.total_bits = (uint64_t)srclen * 8; b.pos = 0;
@@ -82,6 +87,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 		if (state != 2) b.bb_sync();
 		if (state == 0) {
 			const uint64_t hdr = b.pos;
+			hook(hdr, out);
 			if (!b.have(3)) { stop.sfbt = 0xe; stop.subc = (uint32_t)(b.total_bits - hdr); break; }
 			const uint32_t v = b.peek();
 			bfinal = v & 1; btype = (v >> 1) & 3;

@@ -61,6 +61,13 @@ GZS_OK, GZS_MEMBER_FAILED, GZS_MORE_MEMBERS, GZS_TARGET_SPACE, GZS_INVALID = ran
 RANGE_UOFF, RANGE_VOFF = 0, 1
 RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED = range(4)
 
+# checkpoints inside raw / zlib / gzip streams (include/nxz_engine.h: nxz_batch_checkpoint_index / nxz_checkpoint_read_ranges)
+CHECKPOINT_STREAM_DTYPE = np.dtype([("status", "<u4"), ("count", "<u4"), ("format", "<u4"), ("hdr_len", "<u4"), ("out_len", "<u8"),
+                                    ("cc", "<u4"), ("frame_status", "<u4")])
+assert CHECKPOINT_STREAM_DTYPE.itemsize == 32
+CPS_OK, CPS_STREAM_FAILED, CPS_MORE, CPS_NO_OUTPUT, CPS_INVALID = range(5)
+CHECKPOINT_WINDOW = 32768
+
 
 # jobs[].reserved (include/nxz_engine.h)
 JOB_SUSPEND_WHEN_FULL, JOB_NO_DICT = 1, 2
@@ -168,6 +175,11 @@ def load_library():
         L.nxz_bgzf_read_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                            C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint64), C.c_void_p]
+        L.nxz_batch_checkpoint_index.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_checkpoint_read_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_inflate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -472,6 +484,54 @@ class Engine:
         return self.L.nxz_bgzf_read_ranges(self.ctx, packed.data_ptr(), length, coff.data_ptr(), uoff.data_ptr(), coff.numel(), kind,
                                            ranges.data_ptr(), ranges.shape[0], dst.data_ptr() if dst is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
                                            C.byref(out_len), C.byref(decoded), self.stream_handle())
+
+    # ---- checkpoints: an index into raw / zlib / gzip streams, and ranges read through it ----
+    def checkpoint_index(self, fmt, jobs, n, span, cp_cap, windows=False, cbit=None, uoff=None, streams=None):
+        """nxz_batch_checkpoint_index (fmt: FMT_RAW / FMT_ZLIB / FMT_GZIP / FMT_AUTO).  Returns (rc, cbit, uoff, windows, streams):
+        rc 0 / -errno; cbit / uoff int64 device tensors of shape (n, cp_cap + 1); windows a uint8 device tensor of shape
+        (n, cp_cap, 32768) when asked for (True, or a tensor to write to; jobs[i].dst then holds the decoded output), else None;
+        streams a uint8 device tensor of n CHECKPOINT_STREAM_DTYPE records.  Asynchronous on torch's current stream."""
+        t = self.torch
+        if cbit is None:
+            cbit = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if uoff is None:
+            uoff = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if windows is True:
+            windows = t.zeros((max(n, 1), cp_cap, CHECKPOINT_WINDOW), dtype=t.uint8, device=self.dev)
+        elif windows is False:
+            windows = None
+        if streams is None:
+            streams = t.zeros(max(n, 1) * CHECKPOINT_STREAM_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_checkpoint_index(self.ctx, fmt, jobs.data_ptr() if jobs is not None else None, n, span, cp_cap, cbit.data_ptr(),
+                                               uoff.data_ptr(), windows.data_ptr() if windows is not None else None, streams.data_ptr(),
+                                               self.stream_handle())
+        return rc, cbit, uoff, windows, streams
+
+    def checkpoint_read_ranges(self, src, length, cbit, uoff, windows, ranges, dst=None):
+        """ranges of ONE stream (src: uint8 device tensor, `length` bytes, framing included) through its checkpoint index: cbit / uoff
+        int64 device tensors of count + 1 entries, windows a contiguous uint8 device tensor of count slots of 32768 bytes (None for
+        an index of one segment), ranges an (n, 2) int64 device tensor of [begin, end) in uncompressed offsets.  Returns what
+        bgzf_read_ranges returns: (rc, offsets, status, out_len, decoded, dst)."""
+        t = self.torch
+        n = ranges.shape[0]
+        offsets = t.zeros(n + 1, dtype=t.int64, device=self.dev)
+        status = t.zeros(max(n, 1), dtype=t.int32, device=self.dev)
+        out_len, decoded = C.c_uint64(), C.c_uint64()
+        assert cbit.numel() == uoff.numel() and cbit.is_contiguous() and uoff.is_contiguous() and ranges.is_contiguous() and ranges.dtype == t.int64
+        assert windows is None or windows.is_contiguous()
+
+        def call(d, cap):
+            return self.L.nxz_checkpoint_read_ranges(self.ctx, src.data_ptr(), length, cbit.data_ptr(), uoff.data_ptr(),
+                                                     windows.data_ptr() if windows is not None else None, cbit.numel(), ranges.data_ptr(), n,
+                                                     d.data_ptr() if d is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
+                                                     C.byref(out_len), C.byref(decoded), self.stream_handle())
+        if dst is None:                  # (a first call for the size; the second call runs the map again)
+            rc = call(None, 0)
+            dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
+            if rc != -errno.E2BIG:
+                return rc, offsets, status[:n], out_len.value, decoded.value, dst
+        rc = call(dst, dst.numel())
+        return rc, offsets, status[:n], out_len.value, decoded.value, dst
 
     def pack_gzip(self, jobs, results, n, packed, offsets=None):
         """BGZF members from a compress batch, nxz_batch_pack_gzip.  Returns the offsets (int64 device tensor, n + 1)."""
