@@ -1,7 +1,7 @@
-// nxz_batch.cpp -- the batched, device-resident interface of include/nxz_engine.h: the compress and inflate batches and which
-// kernels they get, their dictionary, framed and BGZF forms, table generation, wrap and the pack forms, and the diagnostics.
+// nxz_batch.cpp -- the raw batches of include/nxz_engine.h's device-resident interface: the compress and inflate batches and which
+// kernels they get, their dictionary forms, table generation, wrap and the pack forms, nxz_trim, stage timing and the diagnostics.
+// (The calls around them -- framed streams, sizes, members, one-stream deflate, BGZF and checkpoints -- are nxz_batch_framed.cpp's.)
 #include "nxz_ctx.h"
-#include "nxz_streams.h"
 
 // ---------------------------------------------------------------------------
 // batched, device-resident interface
@@ -160,14 +160,12 @@ static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, si
 	if (sized) return sized;
 	if (dict) {
 		nxz_batch_job_t *djobs = sc.buf[BUF_DICT_JOBS].as<nxz_batch_job_t>();
-		int rc = nxz_launch_dict_jobs(ujobs, n, dict->W, djobs, s);
-		if (rc) { set_err("dictionary jobs launch", (hipError_t)rc); return -EIO; }
+		if (int rc = launched("dictionary jobs launch", nxz_launch_dict_jobs(ujobs, n, dict->W, djobs, s))) return rc;
 		jobs = djobs;
 	}
 	if (isdht && !gen) {
 		prepared = sc.buf[BUF_PREPARED].as<nxz_dht_prepared_t>();
-		int rc = nxz_launch_dht_prepare(dht, ntables, prepared, s);
-		if (rc) { set_err("dht prepare launch", (hipError_t)rc); return -EIO; }
+		if (int rc = launched("dht prepare launch", nxz_launch_dht_prepare(dht, ntables, prepared, s))) return rc;
 	}
 	for (size_t off = 0; off < n; off += chunk) {
 		const size_t m = n - off < chunk ? n - off : chunk;
@@ -192,23 +190,18 @@ static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, si
 		uint32_t *const lz_counts = fused_gen && !count ? nullptr : cnt;
 		int rc = dict ? nxz_launch_lz77_dict(mode, jobs + off, m, lz_scratch, sc.d_cand2, results + off, lz_counts, jc, dict->deflate_window(), s)
 			      : nxz_launch_lz77(mode, jobs + off, m, lz_scratch, sc.d_cand2, results + off, lz_counts, jc, s);
-		if (rc) { set_err("lz77 launch", (hipError_t)rc); return -EIO; }
+		if ((rc = launched("lz77 launch", rc)) != 0) return rc;
 		stamp();
 		if (fused) { stamp(); stamp(); continue; }
 		if (gen) {
-			rc = nxz_launch_dhtgen(cnt, m, sc.d_gen, nullptr, s);
-			if (rc) { set_err("dhtgen launch", (hipError_t)rc); return -EIO; }
+			if ((rc = launched("dhtgen launch", nxz_launch_dhtgen(cnt, m, sc.d_gen, nullptr, s))) != 0) return rc;
 		}
 		stamp();
-		rc = nxz_launch_encode(isdht, gen, jobs + off, m, sc.d_tokens, gen ? sc.d_gen : prepared, results + off, s);
-		if (rc) { set_err("encode launch", (hipError_t)rc); return -EIO; }
+		rc = launched("encode launch", nxz_launch_encode(isdht, gen, jobs + off, m, sc.d_tokens, gen ? sc.d_gen : prepared, results + off, s));
+		if (rc) return rc;
 		stamp();
 	}
-	if (dict) {
-		int rc = nxz_launch_dict_finish(ujobs, n, dict->W, results, s);
-		if (rc) { set_err("dictionary finish launch", (hipError_t)rc); return -EIO; }
-	}
-	return 0;
+	return dict ? launched("dictionary finish launch", nxz_launch_dict_finish(ujobs, n, dict->W, results, s)) : 0;
 }
 
 // nxz_trim(): the token scratch of every stream no batch call is working on goes back to the device (a chunk of 65536 jobs
@@ -288,13 +281,9 @@ extern "C" int nxz_batch_dhtgen(nxz_ctx_t *c, const uint32_t *counts, size_t n, 
 	if (!c || !counts || !tables) return -EINVAL;
 	if (forked_child()) return -ENODEV;
 	(void)hipSetDevice(c->device);
-	int rc = nxz_launch_dhtgen(counts, n, nullptr, tables, (hipStream_t)stream);
-	if (rc) { set_err("dhtgen launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("dhtgen launch", nxz_launch_dhtgen(counts, n, nullptr, tables, (hipStream_t)stream));
 }
 
-// force: 0 -- the kernel by the batch's size and kind; 1 -- a stream per lane, any block type; 2 -- a stream per wavefront
-static int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force);
 extern "C" int nxz_batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n,
 				    nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream)
 {
@@ -318,20 +307,24 @@ static bool sample_btype(nxz_ctx *c, const nxz_batch_job_t *jobs, size_t n, hipS
 	return true;
 }
 
-// The workspace of the workgroup-per-stream kernels for n streams on `s`, and from 128 streams on the order workspace (NULL: none
-// to be had, the streams go as they come).  The caller holds the lease.
-static int wg_workspaces(nxz_ctx *c, hipStream_t s, size_t n, uint8_t **wws, uint8_t **ows)
+const uint32_t *order_by_length_for(nxz_ctx *c, hipStream_t s, const nxz_batch_job_t *jobs, size_t n)
 {
-	return with_scratch(c, s, [&](nxz_ctx::Scratch &sc) -> int {
-		const size_t oneed = n >= 128 ? nxz_order_workspace(n) : 0;
-		if (sc.buf[BUF_WG].grow(s, nxz_inflate_wg_workspace(n)) == DevBuf::FAILED) return -ENOMEM;
-		*wws = sc.buf[BUF_WG].p;
-		*ows = oneed && sc.buf[BUF_ORDER].grow(s, oneed) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
-		return 0;
+	uint8_t *const ows = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
+	});
+	return nxz_launch_order_by_length(jobs, n, ows, s);                  // (NULL without a workspace)
+}
+
+// The workspace of the workgroup-per-stream kernels for n streams on `s` (NULL: none to be had).  The caller holds the lease.
+static uint8_t *wg_workspace(nxz_ctx *c, hipStream_t s, size_t n)
+{
+	return with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_WG].grow(s, nxz_inflate_wg_workspace(n));
+		return sc.buf[BUF_WG].p;
 	});
 }
 
-static int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force)
+int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force)
 {
 	if (!c) return -EINVAL;
 	if (forked_child()) return -ENODEV;
@@ -362,12 +355,10 @@ static int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n,
 	}
 	if (wg) {
 		const auto use = lease_scratch(c, s);
-		uint8_t *wws = nullptr, *ows = nullptr;
-		if ((rc = wg_workspaces(c, s, n, &wws, &ows)) != 0) return rc;
-		const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (a workgroup draws stream after stream: the long ones first)
-		rc = nxz_launch_inflate_wg(jobs, n, results, dht_io, wws, order, nullptr, s);
-		if (rc) { set_err("inflate launch", (hipError_t)rc); return -EIO; }
-		return 0;
+		uint8_t *const wws = wg_workspace(c, s, n);
+		if (!wws) return -ENOMEM;
+		const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (a workgroup draws stream after stream: the long ones first)
+		return launched("inflate launch", nxz_launch_inflate_wg(jobs, n, results, dht_io, wws, order, nullptr, s));
 	}
 	if (lanes && !lm && !force) {
 		// what kind of streams?
@@ -474,33 +465,26 @@ static int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n,
 		const int order_env = oe ? atoi(oe) : -1;
 		if (order_env < 0 ? n > lds_max : order_env != 0) {
 			const auto use = lease_scratch(c, s);                          // (the kernel reads the order)
-			uint8_t *const ows = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-				return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
-			});
-			order = nxz_launch_order_by_length(jobs, n, ows, s);              // (NULL: in the caller's order)
+			order = order_by_length_for(c, s, jobs, n);                       // (NULL: in the caller's order)
 			rc = nxz_launch_inflate(jobs, n, results, dht_io, n <= lds_max, order, s);
 		} else rc = nxz_launch_inflate(jobs, n, results, dht_io, n <= lds_max, nullptr, s);
 	}
-	if (rc) { set_err("inflate launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("inflate launch", rc);
 }
 
 // Streams that share a preset dictionary: a workgroup each with the window preloaded (nxzw::inflate_wg_dict_kernel), the hand-backs a
 // wavefront each behind it (nxzi::inflate_dict_kernel), checksums -- all on `s`, nothing waits.  The caller holds no lock.
-static int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s)
+int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s)
 {
 	const auto use = lease_scratch(c, s);
-	uint8_t *wws = nullptr, *ows = nullptr;
-	int rc = wg_workspaces(c, s, n, &wws, &ows);
-	if (rc) return rc;
-	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;
+	uint8_t *const wws = wg_workspace(c, s, n);
+	if (!wws) return -ENOMEM;
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;
 	// Streams of fewer than NXZ_DICT_WG_MIN source bytes go a wavefront each from the start: the workgroup kernel costs a stream 84 000 -
 	// 95 000 cycles whatever its size and has one stream a CU in flight, the wavefront kernel twenty (profiles/r08_dict.txt).  0: all a workgroup each.
 	const char *wm = getenv("NXZ_DICT_WG_MIN");                         // (read at every call: the tests switch it)
 	const uint32_t src_min = wm ? (uint32_t)strtoul(wm, nullptr, 0) : (uint32_t)NXZ_DICT_WG_MIN_DEFAULT;
-	rc = nxz_launch_inflate_wg_dict(jobs, n, results, wws, order, dict->d_win, dict->win, src_min, s);
-	if (rc) { set_err("inflate launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("inflate launch", nxz_launch_inflate_wg_dict(jobs, n, results, wws, order, dict->d_win, dict->win, src_min, s));
 }
 extern "C" int nxz_batch_decompress_dict(nxz_ctx_t *c, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
 					 nxz_batch_result_t *results, void *stream)
@@ -512,22 +496,27 @@ extern "C" int nxz_batch_decompress_dict(nxz_ctx_t *c, const nxz_dict_t *dict, c
 	return batch_decompress_dict(c, dict, jobs, n, results, (hipStream_t)stream);
 }
 
+// The diagnostics below look at what the last batch on `stream` left in that stream's scratch: waits for the stream, then *p = its
+// buffer `which` as it stands (find, not []: a stream without scratch gets none made).  -EIO: the wait failed; -ENOENT: no such buffer.
+static int settled_buffer(nxz_ctx_t *c, void *stream, ScratchBuf which, const uint8_t **p)
+{
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
+	std::lock_guard<std::mutex> g(c->mtx);
+	auto it = c->scratch.find(s);
+	*p = it != c->scratch.end() ? it->second.buf[which].p : nullptr;
+	return *p ? 0 : -ENOENT;
+}
+
 // (diagnostic / tests: how many streams of the last batch of n that `stream` ran through the lane kernels the fixed-code-only
 // kernel handed back to the general one; waits for the stream)
 extern "C" int nxz_inflate_lanes_handed_back(const uint8_t *workspace, size_t n, uint32_t *count);
 extern "C" int nxz_ctx_lanes_handed_back(nxz_ctx_t *c, void *stream, size_t n, uint32_t *count)
 {
 	if (!c || !count) return -EINVAL;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
 	const uint8_t *ws = nullptr;
-	{
-		std::lock_guard<std::mutex> g(c->mtx);
-		auto it = c->scratch.find(s);
-		if (it != c->scratch.end()) ws = it->second.buf[BUF_LANES].p;
-	}
-	if (!ws) return -ENOENT;
+	if (int rc = settled_buffer(c, stream, BUF_LANES, &ws)) return rc;
 	return nxz_inflate_lanes_handed_back(ws, n, count) ? -EIO : 0;
 }
 
@@ -536,31 +525,15 @@ extern "C" int nxz_ctx_lanes_handed_back(nxz_ctx_t *c, void *stream, size_t n, u
 extern "C" int nxz_ctx_wg_reasons(nxz_ctx_t *c, void *stream, uint32_t *out16)
 {
 	if (!c || !out16) return -EINVAL;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
 	const uint8_t *ws = nullptr;
-	{
-		std::lock_guard<std::mutex> g(c->mtx);
-		auto it = c->scratch.find(s);
-		if (it != c->scratch.end()) ws = it->second.buf[BUF_WG].p;
-	}
-	if (!ws) return -ENOENT;
+	if (int rc = settled_buffer(c, stream, BUF_WG, &ws)) return rc;
 	return nxz_inflate_wg_reasons(ws, out16) ? -EIO : 0;
 }
 extern "C" int nxz_ctx_wg_prof(nxz_ctx_t *c, void *stream, unsigned long long *out12)
 {
 	if (!c || !out12) return -EINVAL;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	if (hipStreamSynchronize(s) != hipSuccess) return -EIO;
 	const uint8_t *ws = nullptr;
-	{
-		std::lock_guard<std::mutex> g(c->mtx);
-		auto it = c->scratch.find(s);
-		if (it != c->scratch.end()) ws = it->second.buf[BUF_WG].p;
-	}
-	if (!ws) return -ENOENT;
+	if (int rc = settled_buffer(c, stream, BUF_WG, &ws)) return rc;
 	return nxz_inflate_wg_prof(ws, out12) ? -EIO : 0;
 }
 
@@ -571,9 +544,7 @@ extern "C" int nxz_batch_wrap(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t 
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;   // NULL = the HIP default stream
 	static const bool old_wrap = getenv("NXZ_WRAP_OLD") && atoi(getenv("NXZ_WRAP_OLD")) != 0;
-	int rc = old_wrap ? nxz_launch_wrap(jobs, n, results, s) : nxz_launch_wrap_sliced(jobs, n, results, s);
-	if (rc) { set_err("wrap launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("wrap launch", old_wrap ? nxz_launch_wrap(jobs, n, results, s) : nxz_launch_wrap_sliced(jobs, n, results, s));
 }
 
 // Gzip members from the results of a compress batch (nxz_misc.hip): offsets[n + 1] and `packed`
@@ -583,9 +554,7 @@ extern "C" int nxz_batch_pack_gzip(nxz_ctx_t *c, const nxz_batch_job_t *jobs, co
 {
 	if (!c || !jobs || !results || !offsets || !packed || n > 0xffffffffu) return -EINVAL;
 	(void)hipSetDevice(c->device);
-	int rc = nxz_launch_pack_members(jobs, results, n, offsets, packed, (hipStream_t)stream);
-	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("pack launch", nxz_launch_pack_members(jobs, results, n, offsets, packed, (hipStream_t)stream));
 }
 
 extern "C" int nxz_batch_pack_zlib(nxz_ctx_t *c, int level, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, size_t n,
@@ -597,9 +566,7 @@ extern "C" int nxz_batch_pack_zlib(nxz_ctx_t *c, int level, const nxz_batch_job_
 	const uint32_t flevel = level < 0 || level == 6 ? 2 : level < 2 ? 0 : level < 6 ? 1 : 3;
 	uint32_t hdr = 0x78u << 8 | flevel << 6;
 	hdr += 31 - hdr % 31;
-	int rc = nxz_launch_pack_zlib(jobs, results, n, hdr & 0xff, offsets, packed, (hipStream_t)stream);
-	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
-	return 0;
+	return launched("pack launch", nxz_launch_pack_zlib(jobs, results, n, hdr & 0xff, offsets, packed, (hipStream_t)stream));
 }
 
 extern "C" int nxz_batch_pack_zlib_dict(nxz_ctx_t *c, int level, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
@@ -607,509 +574,5 @@ extern "C" int nxz_batch_pack_zlib_dict(nxz_ctx_t *c, int level, const nxz_dict_
 {
 	if (!c || !dict || dict->device != c->device || !jobs || !results || !offsets || !packed || n > 0xffffffffu || level < -1 || level > 9) return -EINVAL;
 	(void)hipSetDevice(c->device);
-	int rc = nxz_launch_pack_zlib_dict(jobs, results, n, nxz_zlib_cmf_flg(level, 1) & 0xff, dict->id, offsets, packed, (hipStream_t)stream);
-	if (rc) { set_err("pack launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
-// The caller holds c->frame_use[s].
-// ---------------------------------------------------------------------------
-static int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
-			 nxz_batch_frame_t *frames, hipStream_t s, const nxz_dict *dict = nullptr)
-{
-	// (the caller's frame_use[s] guards the derived jobs: no lease here, batch_decompress takes its own)
-	nxz_batch_job_t *const derived = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_FRAME_JOBS].grow(s, n * sizeof(nxz_batch_job_t));
-		return sc.buf[BUF_FRAME_JOBS].as<nxz_batch_job_t>();
-	});
-	if (!derived) return -ENOMEM;
-	int rc = dict ? nxz_launch_frame_header_dict(fmt, jobs, n, frames, derived, dict->id, s) : nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
-	if (rc) { set_err("frame header launch", (hipError_t)rc); return -EIO; }
-	rc = dict ? batch_decompress_dict(c, dict, derived, n, results, s) : batch_decompress(c, derived, n, results, nullptr, s, 0);
-	if (rc) return rc;
-	rc = nxz_launch_frame_trailer(jobs, n, results, frames, s);
-	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-static std::mutex *frame_mutex(nxz_ctx_t *c, hipStream_t s)
-{
-	std::lock_guard<std::mutex> g(c->mtx);
-	return &c->frame_use[s];
-}
-
-extern "C" int nxz_batch_decompress_framed(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n,
-					   nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
-{
-	if (!c || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	return framed_locked(c, fmt, jobs, n, results, frames, s);
-}
-
-extern "C" int nxz_batch_decompress_framed_dict(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
-						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
-{
-	if (!c || !dict || dict->device != c->device || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	return framed_locked(c, fmt, jobs, n, results, frames, s, dict);
-}
-
-// ---------------------------------------------------------------------------
-// Output sizes (nxz_inflate_size.hip): what the streams would produce, a wavefront each, all on `s`, nothing waits.  From 128
-// streams on the long ones start first (the order is this stream's scratch, as for the decode routes).  The caller holds no lease.
-// ---------------------------------------------------------------------------
-static int batch_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint32_t dict_window, hipStream_t s)
-{
-	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
-	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
-	}) : nullptr;
-	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
-	const int rc = nxz_launch_inflate_size(jobs, n, results, order, dict_window, s);
-	if (rc) { set_err("inflate size launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-extern "C" int nxz_batch_decompress_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, void *stream)
-{
-	if (!c || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	return batch_size(c, jobs, n, results, 0, (hipStream_t)stream);
-}
-
-// header kernel (the framed decode's own, with the dictionary's DICTID when there is one) -> the size walk on the derived jobs ->
-// the trailer step without the checksum comparison.  frame_use[s] guards the derived jobs, as in framed_locked.
-extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
-						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
-{
-	if (!c || (dict && dict->device != c->device) || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	nxz_batch_job_t *const derived = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_FRAME_JOBS].grow(s, n * sizeof(nxz_batch_job_t));
-		return sc.buf[BUF_FRAME_JOBS].as<nxz_batch_job_t>();
-	});
-	if (!derived) return -ENOMEM;
-	int rc = dict ? nxz_launch_frame_header_dict(fmt, jobs, n, frames, derived, dict->id, s) : nxz_launch_frame_header(fmt, jobs, n, frames, derived, s);
-	if (rc) { set_err("frame header launch", (hipError_t)rc); return -EIO; }
-	// (without a dictionary the header kernel sets no NXZ_JOB_NO_DICT, and there is no window to withhold: 0)
-	if ((rc = batch_size(c, derived, n, results, dict ? dict->win : 0, s)) != 0) return rc;
-	rc = nxz_launch_size_trailer(jobs, n, results, frames, s);
-	if (rc) { set_err("frame trailer launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Multi-member gzip jobs (nxz_gzip_members.hip, the rules in nxz_gzip_members.h).  The index is the size query's shape: a wavefront
-// a job, from 128 jobs on the long ones first, the order in this stream's scratch under the lease.  The decode holds frame_use[s]
-// from its first kernel to its last -- BUF_GZIP_MEMBERS is the framed batch framed_locked works on -- and never waits for the host.
-// ---------------------------------------------------------------------------
-extern "C" int nxz_batch_gzip_members_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
-					   nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, void *stream)
-{
-	if (!c || member_cap == 0 || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
-	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
-	}) : nullptr;
-	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
-	const int rc = nxz_launch_gzip_members_index(jobs, n, member_cap, members, streams, order, s);
-	if (rc) { set_err("gzip members index launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-extern "C" int nxz_batch_gzip_members_decode(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
-					     nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, size_t total_members, void *stream)
-{
-	if (!c || member_cap == 0 || total_members < n || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	const uint64_t slots = (uint64_t)n * member_cap;                     // (n < 2^31, member_cap < 2^32: no overflow)
-	const size_t total = (size_t)std::min<uint64_t>(total_members, slots);
-	if (total >= (1u << 31) || slots >= (1ull << 39)) return -E2BIG;     // (the framed batch; a thread a record slot in one grid)
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_GZIP_MEMBERS].grow(s, nxz_gzip_members_workspace(n, total));
-		return sc.buf[BUF_GZIP_MEMBERS].p;
-	});
-	if (!ws) return -ENOMEM;
-	nxz_batch_job_t *xjobs = nullptr;
-	nxz_batch_result_t *xresults = nullptr;
-	nxz_batch_frame_t *xframes = nullptr;
-	int rc = nxz_launch_gzip_members_expand(jobs, n, member_cap, members, streams, total, ws, &xjobs, &xresults, &xframes, s);
-	if (rc) { set_err("gzip members expand launch", (hipError_t)rc); return -EIO; }
-	if ((rc = framed_locked(c, NXZ_FMT_GZIP, xjobs, total, xresults, xframes, s)) != 0) return rc;
-	rc = nxz_launch_gzip_members_join(n, member_cap, members, streams, total, ws, s);
-	if (rc) { set_err("gzip members join launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// One stream per device buffer (nxz_streams.hip, the rules in nxz_streams.h).  The host makes one pass over the streams -- the
-// refusals and the block prefix first[n + 1] -- into pinned staging, uploads it with the descriptors, and queues per chunk of
-// NXZ_STREAMS_CHUNK blocks: expand -> nxz_batch_compress on the device jobs -> layout and checksum joins -> pack; a prologue in
-// front (headers, state) and an epilogue behind (empty streams, trailers, results).  Everything goes on `s`.
-// No host wait: once the stream's scratch holds a batch of this size there is no hipStreamSynchronize, hipMalloc or hipFree on
-// this path (DevBuf::grow and nxz_batch_compress's chunk only act when they must grow).  The one wait there can be is for the
-// UPLOAD of the call before the last on this stream, whose pinned staging this call fills again (Scratch::h_up: two in turn, an
-// event behind each upload); a caller who queues three calls faster than the device takes two uploads meets it, no other.
-// frame_use[s] guards BUF_STREAMS and the staging, as it guards the derived jobs of the framed calls: nxz_batch_compress takes
-// the scratch lease itself.
-// ---------------------------------------------------------------------------
-static uint32_t streams_chunk()
-{
-	const char *e = getenv("NXZ_STREAMS_CHUNK");                        // (read at every call: the tests switch it)
-	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
-	return v ? (uint32_t)std::min<uint64_t>(v, 65536) : NXZ_STREAMS_CHUNK_DEFAULT;
-}
-
-extern "C" size_t nxz_deflate_stream_bound(uint64_t src_len, uint32_t hist_max, int fmt)
-{
-	return (size_t)nxz_streams_bound(src_len, hist_max, fmt);
-}
-
-extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
-					 nxz_stream_result_t *results, void *stream)
-{
-	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !nxz_streams_fmt_ok(fmt) || level < -1 || level > 9 ||
-	    (n && (!jobs || !results))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	if (n >= (1u << 31)) return -E2BIG;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max), ns = (uint32_t)n;
-	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-	// what is uploaded: [descriptors][first], the same layout in the staging and in the device buffer
-	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), up_bytes = o_first + (n + 1) * sizeof(uint32_t);
-	// this call's staging: the upload that read it last must have run
-	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
-	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
-	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), return -ENOMEM);
-	else HIPCHK(hipEventSynchronize(st.ev), return -EIO);
-	if (st.cap < up_bytes) {
-		if (st.h) (void)hipHostFree(st.h);
-		st.h = nullptr; st.cap = 0;
-		if (hipHostMalloc((void **)&st.h, up_bytes) == hipSuccess) st.cap = up_bytes;
-		else { (void)hipGetLastError(); st.h = nullptr; }
-	}
-	with_scratch(c, s, [&](nxz_ctx::Scratch &r) { r.h_up[st.k] = st.h; r.h_up_cap[st.k] = st.cap; r.up_ev[st.k] = st.ev; return 0; });
-	if (!st.h) return -ENOMEM;
-	// one pass over the streams: a refused stream gets no blocks
-	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st.h;
-	uint32_t *const h_first = (uint32_t *)(st.h + o_first);
-	memcpy(h_desc, jobs, n * sizeof(nxz_stream_job_t));
-	uint64_t total = 0;
-	for (size_t i = 0; i < n; i++) {
-		h_first[i] = (uint32_t)total;
-		if (!nxz_streams_refusal(&jobs[i], hist_max, fmt)) total += nxz_streams_blocks(jobs[i].src_len, B);
-		if (total >= (1ull << 31)) return -E2BIG;
-	}
-	h_first[n] = (uint32_t)total;
-	const uint32_t nblk = (uint32_t)total, C = std::min(streams_chunk(), nblk);
-	const size_t o_state = up(up_bytes), o_jobs = o_state + up(n * sizeof(nxz_stream_state_t)), o_res = o_jobs + up((size_t)C * sizeof(nxz_batch_job_t)),
-		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
-		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), d_bytes = o_slots + (size_t)C * NXZ_STREAMS_SLOT;
-	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
-		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
-		return r.buf[BUF_STREAMS].p;
-	});
-	if (!d) return -ENOMEM;
-	const nxz_stream_job_t *const d_desc = (const nxz_stream_job_t *)d;
-	const uint32_t *const d_first = (const uint32_t *)(d + o_first);
-	nxz_stream_state_t *const d_state = (nxz_stream_state_t *)(d + o_state);
-	nxz_batch_job_t *const d_jobs = (nxz_batch_job_t *)(d + o_jobs);
-	nxz_batch_result_t *const d_res = (nxz_batch_result_t *)(d + o_res);
-	uint32_t *const d_owner = (uint32_t *)(d + o_owner);
-	uint64_t *const d_off = (uint64_t *)(d + o_off);
-	uint8_t *const d_slots = d + o_slots;
-	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
-	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
-	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
-	int rc = nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s);
-	if (rc) { set_err("streams prologue launch", (hipError_t)rc); return -EIO; }
-	const uint32_t op_block = nxz_crc_shift_op(B);
-	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
-	for (uint32_t b0 = 0; b0 < nblk; b0 += C) {
-		const uint32_t m = std::min(C, nblk - b0);
-		while (h_first[i_lo + 1] <= b0) i_lo++;
-		uint32_t i_hi = i_lo;
-		while (h_first[i_hi + 1] < b0 + m) i_hi++;
-		rc = nxz_launch_streams_expand(d_desc, d_first, ns, b0, m, hist_max, d_slots, d_jobs, d_owner, s);
-		if (rc) { set_err("streams expand launch", (hipError_t)rc); return -EIO; }
-		if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
-		rc = nxz_launch_streams_layout(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
-		if (!rc) rc = nxz_launch_streams_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, s);
-		if (rc) { set_err("streams pack launch", (hipError_t)rc); return -EIO; }
-		i_lo = i_hi;
-	}
-	rc = nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s);
-	if (rc) { set_err("streams epilogue launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-// The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then
-// ONE wait for ctl = candidates, members, bytes covered, sum of ISIZE.  The caller holds c->frame_use[s].
-static int bgzf_discover_locked(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, size_t max_members,
-				uint64_t *coff, hipStream_t s, uint64_t ctl[4], nxz_batch_job_t **jobs)
-{
-	// room for the candidates: twice the members the caller allows, and one every 32 KiB (a true member has at most
-	// 64 KiB); an image with more -- false candidates in the payloads -- is run again with room for all of them
-	const uint64_t most = len / 4 + 1;                                   // (1f 8b 08 04 cannot overlap itself)
-	uint64_t cap = std::min<uint64_t>(most, std::max<uint64_t>((uint64_t)max_members * 2 + 1024, len / 32768 + 1024));
-	for (int pass = 0; pass < 2; pass++) {
-		uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) -> uint8_t * {
-			cap = std::max(cap, sc.bgzf_cap);
-			const DevBuf::Grown g = sc.buf[BUF_BGZF].grow(s, nxz_bgzf_workspace(len, cap));
-			if (g != DevBuf::KEPT) sc.bgzf_cap = 0;                        // (another buffer, or none: what the old one had room for is history)
-			if (g == DevBuf::FAILED) return nullptr;
-			sc.bgzf_cap = std::max(sc.bgzf_cap, cap);
-			return sc.buf[BUF_BGZF].p;
-		});
-		if (!ws) return -ENOMEM;
-		int rc = nxz_launch_bgzf_discover(packed, len, dst, offsets, max_members, ws, cap, jobs, s);
-		if (!rc && coff) rc = nxz_launch_bgzf_coff(packed, len, ws, cap, max_members, coff, s);
-		if (rc) { set_err("bgzf discovery launch", (hipError_t)rc); return -EIO; }
-		HIPCHK(hipMemcpyAsync(ctl, ws, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s), return -EIO);
-		HIPCHK(hipStreamSynchronize(s), return -EIO);
-		if (ctl[0] <= cap) break;
-		cap = ctl[0];                                                    // (every candidate, the second time)
-	}
-	return 0;
-}
-
-// A BGZF image in device memory: the members found on the device (nxz_launch_bgzf_discover), then ONE wait for their count,
-// then the framed gzip path on them.
-extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
-				     uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
-				     size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream)
-{
-	if (members) *members = 0;
-	if (consumed) *consumed = 0;
-	if (out_len) *out_len = 0;
-	if (!c || (len && !packed) || !offsets || (max_members && (!frames || !results))) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (len < 26) return -EILSEQ;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	uint64_t ctl[4] = {0, 0, 0, 0};
-	nxz_batch_job_t *jobs = nullptr;
-	int rc = bgzf_discover_locked(c, packed, len, dst, offsets, max_members, nullptr, s, ctl, &jobs);
-	if (rc) return rc;
-	const uint64_t L = ctl[1];
-	if (L == 0) return -EILSEQ;
-	if (members) *members = L;
-	if (consumed) *consumed = ctl[2];
-	if (L > max_members) return -E2BIG;
-	if (out_len) *out_len = ctl[3];
-	if (ctl[3] > dst_cap) return -E2BIG;
-	if (L >= (1u << 31)) return -E2BIG;
-	rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)L, results, frames, s);
-	if (rc) return rc;
-	HIPCHK(hipStreamSynchronize(s), return -EIO);
-	return 0;
-}
-
-// The member index of a BGZF image: the discovery of nxz_batch_unpack_gzip (its layout's offsets are uoff) and coff.
-extern "C" int nxz_bgzf_index(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint64_t *coff, uint64_t *uoff, size_t max_members,
-			      uint64_t *members, void *stream)
-{
-	if (members) *members = 0;
-	if (!c || (len && !packed) || !coff || !uoff) return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (len < 26) return -EILSEQ;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	uint64_t ctl[4] = {0, 0, 0, 0};
-	nxz_batch_job_t *jobs = nullptr;
-	int rc = bgzf_discover_locked(c, packed, len, nullptr, uoff, max_members, coff, s, ctl, &jobs);
-	if (rc) return rc;
-	if (ctl[1] == 0) return -EILSEQ;
-	if (members) *members = ctl[1];
-	return ctl[1] > max_members ? -E2BIG : 0;
-}
-
-// Members a chunk of nxz_bgzf_read_ranges decodes at most: NXZ_BGZF_CHUNK (read at every call: the tests lower it), 16 384
-static uint64_t bgzf_chunk_members()
-{
-	const char *e = getenv("NXZ_BGZF_CHUNK");
-	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
-	return v && v < 16384 ? v : 16384;
-}
-
-// Ranges of a BGZF image: the map (nxz_bgzf.hip) and ONE wait for its totals, then per chunk of needed members their
-// framed decode into slots and the gather of the pieces, then the zeros of damaged ranges and a last wait.
-extern "C" int nxz_bgzf_read_ranges(nxz_ctx_t *c, const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff,
-				    uint64_t nidx, int kind, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst, uint64_t dst_cap,
-				    uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
-{
-	if (out_len) *out_len = 0;
-	if (decoded) *decoded = 0;
-	if (!c || !coff || !uoff || !offsets || nidx == 0 || nidx > 0xffffffffull || (packed_len && !packed) || (n && (!ranges || !status)) ||
-	    (kind != NXZ_RANGE_UOFF && kind != NXZ_RANGE_VOFF) || n >= (1ull << 31))
-		return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	const uint64_t L = nidx - 1;
-	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_RNG].grow(s, nxz_bgzf_ranges_workspace(n, L));
-		return sc.buf[BUF_RNG].p;
-	});
-	if (!ws) return -ENOMEM;
-	int rc = nxz_launch_bgzf_map(packed, packed_len, coff, uoff, L, kind, ranges, n, offsets, status, ws, s);
-	if (rc) { set_err("bgzf map launch", (hipError_t)rc); return -EIO; }
-	uint64_t ctl[5];
-	HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
-	HIPCHK(hipStreamSynchronize(s), return -EIO);
-	if (ctl[0]) return -EILSEQ;
-	if (out_len) *out_len = ctl[2];
-	if (ctl[2] > dst_cap || (ctl[2] && !dst)) return -E2BIG;
-	const uint64_t needed = ctl[1], pieces = ctl[3];
-	if (!needed) return 0;
-	// a slot per member of the chunk, all of the largest needed member's size (65 536 for BGZF): at most 1 GiB of them
-	const uint64_t stride = (std::max<uint64_t>(ctl[4], 16) + 15) & ~(uint64_t)15;
-	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / stride)));
-	const size_t sb = (per * stride + 255) & ~(size_t)255, jb = (per * sizeof(nxz_batch_job_t) + 255) & ~(size_t)255,
-		     fb = (per * sizeof(nxz_batch_frame_t) + 255) & ~(size_t)255;
-	uint8_t *const slots = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_RNG_SLOTS].grow(s, sb + jb + fb + per * sizeof(nxz_batch_result_t));
-		return sc.buf[BUF_RNG_SLOTS].p;
-	});
-	if (!slots) return -ENOMEM;
-	nxz_batch_job_t *jobs = (nxz_batch_job_t *)(slots + sb);
-	nxz_batch_frame_t *frames = (nxz_batch_frame_t *)(slots + sb + jb);
-	nxz_batch_result_t *results = (nxz_batch_result_t *)(slots + sb + jb + fb);
-	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
-		const uint64_t cnt = std::min(per, needed - k0);
-		rc = nxz_launch_bgzf_jobs(packed, coff, uoff, n, L, ws, k0, cnt, slots, stride, jobs, s);
-		if (rc) { set_err("bgzf jobs launch", (hipError_t)rc); return -EIO; }
-		rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)cnt, results, frames, s);
-		if (rc) return rc;
-		rc = nxz_launch_bgzf_gather(uoff, n, L, pieces, ws, offsets, slots, stride, k0, cnt, frames, results, dst, status, s);
-		if (rc) { set_err("bgzf gather launch", (hipError_t)rc); return -EIO; }
-	}
-	rc = nxz_launch_bgzf_zero(n, offsets, status, dst, s);
-	if (rc) { set_err("bgzf zero launch", (hipError_t)rc); return -EIO; }
-	HIPCHK(hipStreamSynchronize(s), return -EIO);
-	if (decoded) *decoded = needed;
-	return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Checkpoints (nxz_checkpoint.hip, the rules in nxz_checkpoint.h).  The index is the size query's shape: a wavefront a job, from 128
-// jobs on the long ones first, the order in this stream's scratch under the lease; the windows' copies go behind it on `s`, and
-// nothing waits for the host.
-// ---------------------------------------------------------------------------
-extern "C" int nxz_batch_checkpoint_index(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
-					  uint64_t *cbit, uint64_t *uoff, uint8_t *windows, nxz_checkpoint_stream_t *streams, void *stream)
-{
-	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || span == 0 || cp_cap == 0 || n >= (1u << 31) || (n && (!jobs || !cbit || !uoff || !streams)))
-		return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
-	uint8_t *const ows = n >= 128 ? with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		return sc.buf[BUF_ORDER].grow(s, nxz_order_workspace(n)) != DevBuf::FAILED ? sc.buf[BUF_ORDER].p : nullptr;
-	}) : nullptr;
-	const uint32_t *order = ows ? nxz_launch_order_by_length(jobs, n, ows, s) : nullptr;   // (NULL: in the caller's order)
-	const int rc = nxz_launch_checkpoint_index(fmt, jobs, n, span, cp_cap, cbit, uoff, windows, streams, order, s);
-	if (rc) { set_err("checkpoint index launch", (hipError_t)rc); return -EIO; }
-	return 0;
-}
-
-// Ranges of one stream through its checkpoint index: nxz_bgzf_read_ranges with segments for members.  The map (the index check of
-// nxz_checkpoint.hip inside nxz_bgzf.hip's) and ONE wait for its totals, then per chunk of needed segments their inputs staged,
-// nxz_batch_decompress on them, the verdicts and nxz_bgzf.hip's gather, then the zeros of damaged ranges and a last wait.
-// BUF_RNG and BUF_RNG_SLOTS are the BGZF call's: both calls hold frame_use[s] from the first kernel to the last wait.
-extern "C" int nxz_checkpoint_read_ranges(nxz_ctx_t *c, const uint8_t *src, uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff,
-					  const uint8_t *windows, uint64_t nidx, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst,
-					  uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
-{
-	if (out_len) *out_len = 0;
-	if (decoded) *decoded = 0;
-	if (!c || !src || !cbit || !uoff || !offsets || nidx < 2 || nidx > 0xffffffffull || (!windows && nidx > 2) || (n && (!ranges || !status)) ||
-	    n >= (1ull << 31))
-		return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
-	const uint64_t L = nidx - 1;
-	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_RNG].grow(s, nxz_bgzf_ranges_workspace(n, L));
-		return sc.buf[BUF_RNG].p;
-	});
-	if (!ws) return -ENOMEM;
-	int rc = nxz_launch_range_map_clear(ws, n, L, s);
-	if (!rc) rc = nxz_launch_checkpoint_check(src_len, cbit, uoff, L, ws, s);
-	if (!rc) rc = nxz_launch_range_map_ranges(uoff, L, ranges, n, offsets, status, ws, s);
-	if (!rc) rc = nxz_launch_checkpoint_inmax(cbit, uoff, n, L, ws, s);
-	if (rc) { set_err("checkpoint map launch", (hipError_t)rc); return -EIO; }
-	uint64_t ctl[6];
-	HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
-	HIPCHK(hipStreamSynchronize(s), return -EIO);
-	if (ctl[0]) return -EILSEQ;
-	if (out_len) *out_len = ctl[2];
-	if (ctl[2] > dst_cap || (ctl[2] && !dst)) return -E2BIG;
-	const uint64_t needed = ctl[1], pieces = ctl[3];
-	if (!needed) return 0;
-	// an input and an output slot per segment of the chunk, all of the largest needed segment's size: at most 1 GiB of either (a
-	// segment larger than that goes alone)
-	const uint64_t ostride = (std::max<uint64_t>(ctl[4], 16) + 15) & ~(uint64_t)15, istride = (std::max<uint64_t>(ctl[5], 16) + 15) & ~(uint64_t)15;
-	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / std::max(istride, ostride))));
-	const size_t ib = (per * istride + 255) & ~(size_t)255, ob = (per * ostride + 255) & ~(size_t)255,
-		     jb = (per * sizeof(nxz_batch_job_t) + 255) & ~(size_t)255, fb = (per * sizeof(nxz_batch_frame_t) + 255) & ~(size_t)255;
-	uint8_t *const slots = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_RNG_SLOTS].grow(s, ib + ob + jb + fb + per * sizeof(nxz_batch_result_t));
-		return sc.buf[BUF_RNG_SLOTS].p;
-	});
-	if (!slots) return -ENOMEM;
-	uint8_t *const oslots = slots + ib;
-	nxz_batch_job_t *jobs = (nxz_batch_job_t *)(slots + ib + ob);
-	nxz_batch_frame_t *frames = (nxz_batch_frame_t *)(slots + ib + ob + jb);
-	nxz_batch_result_t *results = (nxz_batch_result_t *)(slots + ib + ob + jb + fb);
-	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
-		const uint64_t cnt = std::min(per, needed - k0);
-		rc = nxz_launch_checkpoint_stage(src, cbit, uoff, windows, n, L, ws, k0, cnt, slots, istride, oslots, ostride, jobs, s);
-		if (rc) { set_err("checkpoint stage launch", (hipError_t)rc); return -EIO; }
-		rc = batch_decompress(c, jobs, (size_t)cnt, results, nullptr, s, 0);
-		if (rc) return rc;
-		rc = nxz_launch_checkpoint_verdict(uoff, n, L, ws, k0, cnt, results, frames, s);
-		if (rc) { set_err("checkpoint verdict launch", (hipError_t)rc); return -EIO; }
-		rc = nxz_launch_bgzf_gather(uoff, n, L, pieces, ws, offsets, oslots, ostride, k0, cnt, frames, results, dst, status, s);
-		if (rc) { set_err("checkpoint gather launch", (hipError_t)rc); return -EIO; }
-	}
-	rc = nxz_launch_bgzf_zero(n, offsets, status, dst, s);
-	if (rc) { set_err("checkpoint zero launch", (hipError_t)rc); return -EIO; }
-	HIPCHK(hipStreamSynchronize(s), return -EIO);
-	if (decoded) *decoded = needed;
-	return 0;
+	return launched("pack launch", nxz_launch_pack_zlib_dict(jobs, results, n, nxz_zlib_cmf_flg(level, 1) & 0xff, dict->id, offsets, packed, (hipStream_t)stream));
 }

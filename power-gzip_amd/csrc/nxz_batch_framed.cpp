@@ -1,0 +1,496 @@
+// nxz_batch_framed.cpp -- the calls of include/nxz_engine.h's device-resident interface that put kernels of their own around a raw
+// batch (nxz_batch.cpp) or walk streams without decoding them: framed zlib / gzip streams, output sizes, multi-member gzip jobs,
+// one stream per device buffer, BGZF discovery, index and range reads, checkpoint index and range reads.
+#include <functional>
+#include "nxz_ctx.h"
+#include "nxz_streams.h"
+
+// ---------------------------------------------------------------------------
+// Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
+// The caller holds c->frame_use[s].
+// ---------------------------------------------------------------------------
+// The header kernel (with the dictionary's DICTID when there is one) into frames and *derived, the raw jobs in BUF_FRAME_JOBS of `s`.
+// (the caller's frame_use[s] guards the derived jobs: no lease here, the raw batch takes its own)
+static int derive_framed_jobs(nxz_ctx_t *c, int fmt, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_frame_t *frames,
+			      hipStream_t s, nxz_batch_job_t **derived)
+{
+	nxz_batch_job_t *const d = *derived = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_FRAME_JOBS].grow(s, n * sizeof(nxz_batch_job_t));
+		return sc.buf[BUF_FRAME_JOBS].as<nxz_batch_job_t>();
+	});
+	if (!d) return -ENOMEM;
+	return launched("frame header launch", dict ? nxz_launch_frame_header_dict(fmt, jobs, n, frames, d, dict->id, s)
+						    : nxz_launch_frame_header(fmt, jobs, n, frames, d, s));
+}
+
+static int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results,
+			 nxz_batch_frame_t *frames, hipStream_t s, const nxz_dict *dict = nullptr)
+{
+	nxz_batch_job_t *derived = nullptr;
+	int rc = derive_framed_jobs(c, fmt, dict, jobs, n, frames, s, &derived);
+	if (rc) return rc;
+	rc = dict ? batch_decompress_dict(c, dict, derived, n, results, s) : batch_decompress(c, derived, n, results, nullptr, s, 0);
+	if (rc) return rc;
+	return launched("frame trailer launch", nxz_launch_frame_trailer(jobs, n, results, frames, s));
+}
+
+static std::mutex *frame_mutex(nxz_ctx_t *c, hipStream_t s)
+{
+	std::lock_guard<std::mutex> g(c->mtx);
+	return &c->frame_use[s];
+}
+
+extern "C" int nxz_batch_decompress_framed(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n,
+					   nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	return framed_locked(c, fmt, jobs, n, results, frames, s);
+}
+
+extern "C" int nxz_batch_decompress_framed_dict(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || !dict || dict->device != c->device || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	return framed_locked(c, fmt, jobs, n, results, frames, s, dict);
+}
+
+// ---------------------------------------------------------------------------
+// Output sizes (nxz_inflate_size.hip): what the streams would produce, a wavefront each, all on `s`, nothing waits.  From 128
+// streams on the long ones start first (the order is this stream's scratch, as for the decode routes).  The caller holds no lease.
+// ---------------------------------------------------------------------------
+static int batch_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, uint32_t dict_window, hipStream_t s)
+{
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
+	return launched("inflate size launch", nxz_launch_inflate_size(jobs, n, results, order, dict_window, s));
+}
+
+extern "C" int nxz_batch_decompress_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, void *stream)
+{
+	if (!c || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	return batch_size(c, jobs, n, results, 0, (hipStream_t)stream);
+}
+
+// header kernel (the framed decode's own: derive_framed_jobs) -> the size walk on the derived jobs ->
+// the trailer step without the checksum comparison.  frame_use[s] guards the derived jobs, as in framed_locked.
+extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+						nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || (dict && dict->device != c->device) || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	nxz_batch_job_t *derived = nullptr;
+	int rc = derive_framed_jobs(c, fmt, dict, jobs, n, frames, s, &derived);
+	if (rc) return rc;
+	// (without a dictionary the header kernel sets no NXZ_JOB_NO_DICT, and there is no window to withhold: 0)
+	if ((rc = batch_size(c, derived, n, results, dict ? dict->win : 0, s)) != 0) return rc;
+	return launched("frame trailer launch", nxz_launch_size_trailer(jobs, n, results, frames, s));
+}
+
+// ---------------------------------------------------------------------------
+// Multi-member gzip jobs (nxz_gzip_members.hip, the rules in nxz_gzip_members.h).  The index is the size query's shape: a wavefront
+// a job, from 128 jobs on the long ones first, the order in this stream's scratch under the lease.  The decode holds frame_use[s]
+// from its first kernel to its last -- BUF_GZIP_MEMBERS is the framed batch framed_locked works on -- and never waits for the host.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_gzip_members_size(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+					   nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, void *stream)
+{
+	if (!c || member_cap == 0 || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
+	return launched("gzip members index launch", nxz_launch_gzip_members_index(jobs, n, member_cap, members, streams, order, s));
+}
+
+extern "C" int nxz_batch_gzip_members_decode(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, uint32_t member_cap,
+					     nxz_gzip_member_t *members, nxz_gzip_stream_t *streams, size_t total_members, void *stream)
+{
+	if (!c || member_cap == 0 || total_members < n || n >= (1u << 31) || (n && (!jobs || !members || !streams))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	const uint64_t slots = (uint64_t)n * member_cap;                     // (n < 2^31, member_cap < 2^32: no overflow)
+	const size_t total = (size_t)std::min<uint64_t>(total_members, slots);
+	if (total >= (1u << 31) || slots >= (1ull << 39)) return -E2BIG;     // (the framed batch; a thread a record slot in one grid)
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_GZIP_MEMBERS].grow(s, nxz_gzip_members_workspace(n, total));
+		return sc.buf[BUF_GZIP_MEMBERS].p;
+	});
+	if (!ws) return -ENOMEM;
+	nxz_batch_job_t *xjobs = nullptr;
+	nxz_batch_result_t *xresults = nullptr;
+	nxz_batch_frame_t *xframes = nullptr;
+	int rc = launched("gzip members expand launch", nxz_launch_gzip_members_expand(jobs, n, member_cap, members, streams, total, ws, &xjobs, &xresults, &xframes, s));
+	if (rc) return rc;
+	if ((rc = framed_locked(c, NXZ_FMT_GZIP, xjobs, total, xresults, xframes, s)) != 0) return rc;
+	return launched("gzip members join launch", nxz_launch_gzip_members_join(n, member_cap, members, streams, total, ws, s));
+}
+
+// ---------------------------------------------------------------------------
+// One stream per device buffer (nxz_streams.hip, the rules in nxz_streams.h).  The host makes one pass over the streams -- the
+// refusals and the block prefix first[n + 1] -- into pinned staging, uploads it with the descriptors, and queues per chunk of
+// NXZ_STREAMS_CHUNK blocks: expand -> nxz_batch_compress on the device jobs -> layout and checksum joins -> pack; a prologue in
+// front (headers, state) and an epilogue behind (empty streams, trailers, results).  Everything goes on `s`.
+// No host wait: once the stream's scratch holds a batch of this size there is no hipStreamSynchronize, hipMalloc or hipFree on
+// this path (DevBuf::grow and nxz_batch_compress's chunk only act when they must grow).  The one wait there can be is for the
+// UPLOAD of the call before the last on this stream, whose pinned staging this call fills again (Scratch::h_up: two in turn, an
+// event behind each upload); a caller who queues three calls faster than the device takes two uploads meets it, no other.
+// frame_use[s] guards BUF_STREAMS and the staging, as it guards the derived jobs of the framed calls: nxz_batch_compress takes
+// the scratch lease itself.
+// ---------------------------------------------------------------------------
+static uint32_t streams_chunk()
+{
+	const char *e = getenv("NXZ_STREAMS_CHUNK");                        // (read at every call: the tests switch it)
+	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
+	return v ? (uint32_t)std::min<uint64_t>(v, 65536) : NXZ_STREAMS_CHUNK_DEFAULT;
+}
+
+extern "C" size_t nxz_deflate_stream_bound(uint64_t src_len, uint32_t hist_max, int fmt)
+{
+	return (size_t)nxz_streams_bound(src_len, hist_max, fmt);
+}
+
+extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
+					 nxz_stream_result_t *results, void *stream)
+{
+	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !nxz_streams_fmt_ok(fmt) || level < -1 || level > 9 ||
+	    (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	if (n >= (1u << 31)) return -E2BIG;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max), ns = (uint32_t)n;
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	// what is uploaded: [descriptors][first], the same layout in the staging and in the device buffer
+	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), up_bytes = o_first + (n + 1) * sizeof(uint32_t);
+	// this call's staging: the upload that read it last must have run
+	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
+	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
+	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), return -ENOMEM);
+	else HIPCHK(hipEventSynchronize(st.ev), return -EIO);
+	if (st.cap < up_bytes) {
+		if (st.h) (void)hipHostFree(st.h);
+		st.h = nullptr; st.cap = 0;
+		if (hipHostMalloc((void **)&st.h, up_bytes) == hipSuccess) st.cap = up_bytes;
+		else { (void)hipGetLastError(); st.h = nullptr; }
+	}
+	with_scratch(c, s, [&](nxz_ctx::Scratch &r) { r.h_up[st.k] = st.h; r.h_up_cap[st.k] = st.cap; r.up_ev[st.k] = st.ev; return 0; });
+	if (!st.h) return -ENOMEM;
+	// one pass over the streams: a refused stream gets no blocks
+	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st.h;
+	uint32_t *const h_first = (uint32_t *)(st.h + o_first);
+	memcpy(h_desc, jobs, n * sizeof(nxz_stream_job_t));
+	uint64_t total = 0;
+	for (size_t i = 0; i < n; i++) {
+		h_first[i] = (uint32_t)total;
+		if (!nxz_streams_refusal(&jobs[i], hist_max, fmt)) total += nxz_streams_blocks(jobs[i].src_len, B);
+		if (total >= (1ull << 31)) return -E2BIG;
+	}
+	h_first[n] = (uint32_t)total;
+	const uint32_t nblk = (uint32_t)total, C = std::min(streams_chunk(), nblk);
+	const size_t o_state = up(up_bytes), o_jobs = o_state + up(n * sizeof(nxz_stream_state_t)), o_res = o_jobs + up((size_t)C * sizeof(nxz_batch_job_t)),
+		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
+		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), d_bytes = o_slots + (size_t)C * NXZ_STREAMS_SLOT;
+	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
+		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
+		return r.buf[BUF_STREAMS].p;
+	});
+	if (!d) return -ENOMEM;
+	const nxz_stream_job_t *const d_desc = (const nxz_stream_job_t *)d;
+	const uint32_t *const d_first = (const uint32_t *)(d + o_first);
+	nxz_stream_state_t *const d_state = (nxz_stream_state_t *)(d + o_state);
+	nxz_batch_job_t *const d_jobs = (nxz_batch_job_t *)(d + o_jobs);
+	nxz_batch_result_t *const d_res = (nxz_batch_result_t *)(d + o_res);
+	uint32_t *const d_owner = (uint32_t *)(d + o_owner);
+	uint64_t *const d_off = (uint64_t *)(d + o_off);
+	uint8_t *const d_slots = d + o_slots;
+	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
+	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
+	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
+	int rc = launched("streams prologue launch", nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s));
+	if (rc) return rc;
+	const uint32_t op_block = nxz_crc_shift_op(B);
+	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
+	for (uint32_t b0 = 0; b0 < nblk; b0 += C) {
+		const uint32_t m = std::min(C, nblk - b0);
+		while (h_first[i_lo + 1] <= b0) i_lo++;
+		uint32_t i_hi = i_lo;
+		while (h_first[i_hi + 1] < b0 + m) i_hi++;
+		rc = launched("streams expand launch", nxz_launch_streams_expand(d_desc, d_first, ns, b0, m, hist_max, d_slots, d_jobs, d_owner, s));
+		if (rc) return rc;
+		if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
+		rc = nxz_launch_streams_layout(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
+		if (!rc) rc = nxz_launch_streams_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, s);
+		if ((rc = launched("streams pack launch", rc)) != 0) return rc;
+		i_lo = i_hi;
+	}
+	return launched("streams epilogue launch", nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s));
+}
+
+// The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then
+// ONE wait for ctl = candidates, members, bytes covered, sum of ISIZE.  The caller holds c->frame_use[s].
+static int bgzf_discover_locked(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t *offsets, size_t max_members,
+				uint64_t *coff, hipStream_t s, uint64_t ctl[4], nxz_batch_job_t **jobs)
+{
+	// room for the candidates: twice the members the caller allows, and one every 32 KiB (a true member has at most
+	// 64 KiB); an image with more -- false candidates in the payloads -- is run again with room for all of them
+	const uint64_t most = len / 4 + 1;                                   // (1f 8b 08 04 cannot overlap itself)
+	uint64_t cap = std::min<uint64_t>(most, std::max<uint64_t>((uint64_t)max_members * 2 + 1024, len / 32768 + 1024));
+	for (int pass = 0; pass < 2; pass++) {
+		uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) -> uint8_t * {
+			cap = std::max(cap, sc.bgzf_cap);
+			const DevBuf::Grown g = sc.buf[BUF_BGZF].grow(s, nxz_bgzf_workspace(len, cap));
+			if (g != DevBuf::KEPT) sc.bgzf_cap = 0;                        // (another buffer, or none: what the old one had room for is history)
+			if (g == DevBuf::FAILED) return nullptr;
+			sc.bgzf_cap = std::max(sc.bgzf_cap, cap);
+			return sc.buf[BUF_BGZF].p;
+		});
+		if (!ws) return -ENOMEM;
+		int rc = nxz_launch_bgzf_discover(packed, len, dst, offsets, max_members, ws, cap, jobs, s);
+		if (!rc && coff) rc = nxz_launch_bgzf_coff(packed, len, ws, cap, max_members, coff, s);
+		if ((rc = launched("bgzf discovery launch", rc)) != 0) return rc;
+		HIPCHK(hipMemcpyAsync(ctl, ws, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s), return -EIO);
+		HIPCHK(hipStreamSynchronize(s), return -EIO);
+		if (ctl[0] <= cap) break;
+		cap = ctl[0];                                                    // (every candidate, the second time)
+	}
+	return 0;
+}
+
+// A BGZF image in device memory: the members found on the device (nxz_launch_bgzf_discover), then ONE wait for their count,
+// then the framed gzip path on them.
+extern "C" int nxz_batch_unpack_gzip(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint8_t *dst, uint64_t dst_cap,
+				     uint64_t *offsets, nxz_batch_frame_t *frames, nxz_batch_result_t *results,
+				     size_t max_members, uint64_t *members, uint64_t *consumed, uint64_t *out_len, void *stream)
+{
+	if (members) *members = 0;
+	if (consumed) *consumed = 0;
+	if (out_len) *out_len = 0;
+	if (!c || (len && !packed) || !offsets || (max_members && (!frames || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (len < 26) return -EILSEQ;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint64_t ctl[4] = {0, 0, 0, 0};
+	nxz_batch_job_t *jobs = nullptr;
+	int rc = bgzf_discover_locked(c, packed, len, dst, offsets, max_members, nullptr, s, ctl, &jobs);
+	if (rc) return rc;
+	const uint64_t L = ctl[1];
+	if (L == 0) return -EILSEQ;
+	if (members) *members = L;
+	if (consumed) *consumed = ctl[2];
+	if (L > max_members) return -E2BIG;
+	if (out_len) *out_len = ctl[3];
+	if (ctl[3] > dst_cap) return -E2BIG;
+	if (L >= (1u << 31)) return -E2BIG;
+	rc = framed_locked(c, NXZ_FMT_GZIP, jobs, (size_t)L, results, frames, s);
+	if (rc) return rc;
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	return 0;
+}
+
+// The member index of a BGZF image: the discovery of nxz_batch_unpack_gzip (its layout's offsets are uoff) and coff.
+extern "C" int nxz_bgzf_index(nxz_ctx_t *c, const uint8_t *packed, uint64_t len, uint64_t *coff, uint64_t *uoff, size_t max_members,
+			      uint64_t *members, void *stream)
+{
+	if (members) *members = 0;
+	if (!c || (len && !packed) || !coff || !uoff) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (len < 26) return -EILSEQ;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	uint64_t ctl[4] = {0, 0, 0, 0};
+	nxz_batch_job_t *jobs = nullptr;
+	int rc = bgzf_discover_locked(c, packed, len, nullptr, uoff, max_members, coff, s, ctl, &jobs);
+	if (rc) return rc;
+	if (ctl[1] == 0) return -EILSEQ;
+	if (members) *members = ctl[1];
+	return ctl[1] > max_members ? -E2BIG : 0;
+}
+
+// Members a chunk of a range read decodes at most: NXZ_BGZF_CHUNK (read at every call: the tests lower it), 16 384
+static uint64_t bgzf_chunk_members()
+{
+	const char *e = getenv("NXZ_BGZF_CHUNK");
+	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
+	return v && v < 16384 ? v : 16384;
+}
+
+// ---------------------------------------------------------------------------
+// Range reads through an index: nxz_bgzf_read_ranges over the members of a BGZF image, nxz_checkpoint_read_ranges over the segments
+// between a stream's checkpoints.  One driver: the map and ONE wait for its totals, then per chunk of needed members their decode
+// into slots and the gather of the pieces (nxz_bgzf.hip's, for both), then the zeros of damaged ranges and a last wait.  The caller
+// holds frame_use[s] from the first kernel to the last wait: BUF_RNG and BUF_RNG_SLOTS are both calls'.
+// ---------------------------------------------------------------------------
+// a chunk's part of BUF_RNG_SLOTS: an output slot (and, where the call stages its inputs, an input slot) per member, all of the
+// largest needed member's size and 16-byte aligned, then the members' jobs, frames and results
+struct RangeSlots {
+	uint8_t *islots, *oslots;
+	uint64_t istride, ostride;
+	nxz_batch_job_t *jobs;
+	nxz_batch_frame_t *frames;
+	nxz_batch_result_t *results;
+};
+// what the two calls do differently.  Both callables queue on `s`, report their own failures (launched) and return 0 or the error:
+//   map(ws)                 the map kernels into ws (BUF_RNG): ctl = ws[0..5] as nxz_device.h lists them
+//   chunk(ws, k0, cnt, sl)  staging, decode and verdict of needed members k0 .. k0 + cnt - 1, so that sl.frames and sl.results are
+//                           what nxz_launch_bgzf_gather looks at
+struct RangeSteps {
+	std::function<int(uint8_t *ws)> map;
+	std::function<int(uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl)> chunk;
+	bool input_slots;                 // the chunk stages its inputs: slots of ctl[5] bytes (else none, istride 0)
+	const char *gather_what, *zero_what;
+};
+static int read_ranges_locked(nxz_ctx_t *c, hipStream_t s, const RangeSteps &steps, const uint64_t *uoff, uint64_t L, size_t n, uint8_t *dst,
+			      uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded)
+{
+	uint8_t *const ws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_RNG].grow(s, nxz_bgzf_ranges_workspace(n, L));
+		return sc.buf[BUF_RNG].p;
+	});
+	if (!ws) return -ENOMEM;
+	int rc = steps.map(ws);
+	if (rc) return rc;
+	uint64_t ctl[6];
+	HIPCHK(hipMemcpyAsync(ctl, ws, sizeof(ctl), hipMemcpyDeviceToHost, s), return -EIO);
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (ctl[0]) return -EILSEQ;
+	if (out_len) *out_len = ctl[2];
+	if (ctl[2] > dst_cap || (ctl[2] && !dst)) return -E2BIG;
+	const uint64_t needed = ctl[1], pieces = ctl[3];
+	if (!needed) return 0;
+	// at most 1 GiB of output slots, and of input slots (65 536 bytes a slot for BGZF; a member larger than 1 GiB goes alone)
+	auto stride_of = [](uint64_t largest) { return (std::max<uint64_t>(largest, 16) + 15) & ~(uint64_t)15; };
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	RangeSlots sl;
+	sl.ostride = stride_of(ctl[4]);
+	sl.istride = steps.input_slots ? stride_of(ctl[5]) : 0;
+	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / std::max(sl.istride, sl.ostride))));
+	const size_t ib = up(per * sl.istride), ob = up(per * sl.ostride), jb = up(per * sizeof(nxz_batch_job_t)), fb = up(per * sizeof(nxz_batch_frame_t));
+	uint8_t *const slots = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_RNG_SLOTS].grow(s, ib + ob + jb + fb + per * sizeof(nxz_batch_result_t));
+		return sc.buf[BUF_RNG_SLOTS].p;
+	});
+	if (!slots) return -ENOMEM;
+	sl.islots = slots; sl.oslots = slots + ib;
+	sl.jobs = (nxz_batch_job_t *)(slots + ib + ob);
+	sl.frames = (nxz_batch_frame_t *)(slots + ib + ob + jb);
+	sl.results = (nxz_batch_result_t *)(slots + ib + ob + jb + fb);
+	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
+		const uint64_t cnt = std::min(per, needed - k0);
+		if ((rc = steps.chunk(ws, k0, cnt, sl)) != 0) return rc;
+		rc = launched(steps.gather_what, nxz_launch_bgzf_gather(uoff, n, L, pieces, ws, offsets, sl.oslots, sl.ostride, k0, cnt, sl.frames, sl.results, dst, status, s));
+		if (rc) return rc;
+	}
+	if ((rc = launched(steps.zero_what, nxz_launch_bgzf_zero(n, offsets, status, dst, s))) != 0) return rc;
+	HIPCHK(hipStreamSynchronize(s), return -EIO);
+	if (decoded) *decoded = needed;
+	return 0;
+}
+
+// Ranges of a BGZF image: the map is nxz_bgzf.hip's, a chunk is the framed gzip decode of its members into the output slots.
+extern "C" int nxz_bgzf_read_ranges(nxz_ctx_t *c, const uint8_t *packed, uint64_t packed_len, const uint64_t *coff, const uint64_t *uoff,
+				    uint64_t nidx, int kind, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst, uint64_t dst_cap,
+				    uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !coff || !uoff || !offsets || nidx == 0 || nidx > 0xffffffffull || (packed_len && !packed) || (n && (!ranges || !status)) ||
+	    (kind != NXZ_RANGE_UOFF && kind != NXZ_RANGE_VOFF) || n >= (1ull << 31))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t L = nidx - 1;
+	RangeSteps steps;
+	steps.map = [&](uint8_t *ws) {
+		return launched("bgzf map launch", nxz_launch_bgzf_map(packed, packed_len, coff, uoff, L, kind, ranges, n, offsets, status, ws, s));
+	};
+	steps.chunk = [&](uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl) {
+		const int rc = launched("bgzf jobs launch", nxz_launch_bgzf_jobs(packed, coff, uoff, n, L, ws, k0, cnt, sl.oslots, sl.ostride, sl.jobs, s));
+		return rc ? rc : framed_locked(c, NXZ_FMT_GZIP, sl.jobs, (size_t)cnt, sl.results, sl.frames, s);
+	};
+	steps.input_slots = false;
+	steps.gather_what = "bgzf gather launch"; steps.zero_what = "bgzf zero launch";
+	return read_ranges_locked(c, s, steps, uoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
+}
+
+// ---------------------------------------------------------------------------
+// Checkpoints (nxz_checkpoint.hip, the rules in nxz_checkpoint.h).  The index is the size query's shape: a wavefront a job, from 128
+// jobs on the long ones first, the order in this stream's scratch under the lease; the windows' copies go behind it on `s`, and
+// nothing waits for the host.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_checkpoint_index(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
+					  uint64_t *cbit, uint64_t *uoff, uint8_t *windows, nxz_checkpoint_stream_t *streams, void *stream)
+{
+	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || span == 0 || cp_cap == 0 || n >= (1u << 31) || (n && (!jobs || !cbit || !uoff || !streams)))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
+	return launched("checkpoint index launch", nxz_launch_checkpoint_index(fmt, jobs, n, span, cp_cap, cbit, uoff, windows, streams, order, s));
+}
+
+// Ranges of one stream through its checkpoint index: nxz_bgzf_read_ranges with segments for members.  The map is the index check of
+// nxz_checkpoint.hip inside nxz_bgzf.hip's; a chunk is its segments' inputs staged, nxz_batch_decompress on them and the verdicts.
+extern "C" int nxz_checkpoint_read_ranges(nxz_ctx_t *c, const uint8_t *src, uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff,
+					  const uint8_t *windows, uint64_t nidx, const nxz_bgzf_range_t *ranges, size_t n, uint8_t *dst,
+					  uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !src || !cbit || !uoff || !offsets || nidx < 2 || nidx > 0xffffffffull || (!windows && nidx > 2) || (n && (!ranges || !status)) ||
+	    n >= (1ull << 31))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t L = nidx - 1;
+	RangeSteps steps;
+	steps.map = [&](uint8_t *ws) {
+		int rc = nxz_launch_range_map_clear(ws, n, L, s);
+		if (!rc) rc = nxz_launch_checkpoint_check(src_len, cbit, uoff, L, ws, s);
+		if (!rc) rc = nxz_launch_range_map_ranges(uoff, L, ranges, n, offsets, status, ws, s);
+		if (!rc) rc = nxz_launch_checkpoint_inmax(cbit, uoff, n, L, ws, s);
+		return launched("checkpoint map launch", rc);
+	};
+	steps.chunk = [&](uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl) {
+		int rc = launched("checkpoint stage launch", nxz_launch_checkpoint_stage(src, cbit, uoff, windows, n, L, ws, k0, cnt, sl.islots, sl.istride,
+											 sl.oslots, sl.ostride, sl.jobs, s));
+		if (!rc) rc = batch_decompress(c, sl.jobs, (size_t)cnt, sl.results, nullptr, s, 0);
+		return rc ? rc : launched("checkpoint verdict launch", nxz_launch_checkpoint_verdict(uoff, n, L, ws, k0, cnt, sl.results, sl.frames, s));
+	};
+	steps.input_slots = true;
+	steps.gather_what = "checkpoint gather launch"; steps.zero_what = "checkpoint zero launch";
+	return read_ranges_locked(c, s, steps, uoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
+}

@@ -1,5 +1,5 @@
 // nxz_bgzf.hip -- BGZF random access on the device: a batch of byte ranges of a BGZF image, read through its member index
-// (nxz_bgzf_read_ranges; nxz_engine.cpp runs the steps on the caller's stream and waits once, after the map).
+// (nxz_bgzf_read_ranges; nxz_batch_framed.cpp runs the steps on the caller's stream and waits once, after the map).
 //
 // Map (nothing is decoded before the index has been checked):
 //   index_check_kernel   a thread a member: nxz_bgzf_member_size at coff[j] - coff[0] == coff[j+1] - coff[j], uoff
@@ -59,23 +59,6 @@ __global__ __launch_bounds__(256) void range_map_kernel(const uint64_t *__restri
 	rb[r] = ub; rfirst[r] = first; rlen[r] = ue - ub; rpieces[r] = pieces;
 }
 
-// exclusive prefix sum across one workgroup of 1024 threads (part: 1024 entries of LDS); returns the thread's start, *total
-__device__ inline uint64_t block_excl(uint64_t v, uint64_t *part, uint64_t *total)
-{
-	const uint32_t t = threadIdx.x;
-	__syncthreads();
-	part[t] = v;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024; d <<= 1) {
-		const uint64_t u = t >= d ? part[t - d] : 0;
-		__syncthreads();
-		part[t] += u;
-		__syncthreads();
-	}
-	*total = part[1023];
-	return part[t] - v;
-}
-
 __global__ __launch_bounds__(1024) void member_scan_kernel(int32_t *__restrict__ diff, const uint64_t *__restrict__ uoff, uint64_t L,
 							   uint64_t *__restrict__ ctl, uint32_t *__restrict__ midx, uint32_t *__restrict__ list)
 {
@@ -86,14 +69,14 @@ __global__ __launch_bounds__(1024) void member_scan_kernel(int32_t *__restrict__
 	int64_t sum = 0;
 	for (uint64_t j = lo; j < hi; j++) sum += diff[j];
 	uint64_t tot;
-	int64_t cover = (int64_t)block_excl((uint64_t)sum, part, &tot);    // (two's complement: the sums of a prefix are >= 0)
+	int64_t cover = (int64_t)nxz_block_excl((uint64_t)sum, part, &tot);    // (two's complement: the sums of a prefix are >= 0)
 	uint64_t cnt = 0;
 	for (uint64_t j = lo; j < hi; j++) {
 		cover += diff[j];
 		diff[j] = cover > 0;                                          // (the difference array becomes the needed flags)
 		cnt += cover > 0;
 	}
-	uint64_t k = block_excl(cnt, part, &tot), big = 0;
+	uint64_t k = nxz_block_excl(cnt, part, &tot), big = 0;
 	for (uint64_t j = lo; j < hi; j++) {
 		if (diff[j]) {
 			midx[j] = (uint32_t)k; list[k++] = (uint32_t)j;
@@ -115,7 +98,7 @@ __global__ __launch_bounds__(1024) void range_scan_kernel(const uint64_t *__rest
 	uint64_t s = 0, p = 0;
 	for (uint64_t r = lo; r < hi; r++) { s += rlen[r]; p += rpieces[r]; }
 	uint64_t ts, tp;
-	uint64_t o = block_excl(s, part, &ts), q = block_excl(p, part, &tp);
+	uint64_t o = nxz_block_excl(s, part, &ts), q = nxz_block_excl(p, part, &tp);
 	for (uint64_t r = lo; r < hi; r++) { offsets[r] = o; poff[r] = q; o += rlen[r]; q += rpieces[r]; }
 	if (t == 0) { offsets[n] = ts; poff[n] = tp; ctl[2] = ts; ctl[3] = tp; }
 }

@@ -3,14 +3,14 @@
 // is the size walk (nxz_inflate_walk.h) with a hook at every block header, and a range read decodes its segments with
 // nxz_batch_decompress as jobs [window][source bytes] that resume inside a byte.
 //
-// The index, all on the caller's stream (nxz_batch.cpp queues it, nothing waits for the host):
+// The index, all on the caller's stream (nxz_batch_framed.cpp queues it, nothing waits for the host):
 //   index_kernel     one job per wavefront, one wavefront per workgroup, the long jobs first -- the shape of the size query
 //                    (nxz_inflate_size.hip) and of the member index (nxz_gzip_members.hip): the header by nxz_frame.h's parser, every
 //                    lane on the same bytes, then nxzs::walk, whose hook applies the checkpoint rule and stores the entry from lane 0;
 //                    the stream's record and the sentinel last.  LDS is the walk's; the accumulator lives in scalar registers.
 //   window_kernel    a workgroup per stored checkpoint (grid-stride): the min(uoff, 32768) bytes in front of uoff[k] from the job's
 //                    decoded output to the start of the checkpoint's slot, 16 bytes a lane where the slot's alignment allows.
-// A range read (nxz_batch.cpp runs the steps and waits once, after the map -- the shape of nxz_bgzf_read_ranges, whose map, gather
+// A range read (nxz_batch_framed.cpp runs the steps and waits once, after the map -- the shape of nxz_bgzf_read_ranges, whose map, gather
 // and zero kernels it uses as they are: nxz_bgzf.hip):
 //   check_kernel     a thread an entry: nxz_cp_entry_ok; any fault sets ctl[0] and every later kernel writes nothing
 //   (the range map and the scans of nxz_bgzf.hip over uoff: needed segments, each once, their list)
@@ -24,34 +24,13 @@
 #include <stdint.h>
 #include "nxz_device.h"
 #include "nxz_frame.h"
+#include "nxz_frame_wave.h"
 #include "nxz_inflate_walk.h"
 #include "nxz_checkpoint.h"
 
 namespace nxzcp {
 
 using nxzi::uni;
-
-// nxz_frame.hip's steps of the header parser that use the whole wavefront (as in nxz_gzip_members.hip)
-struct WaveOps {
-	uint32_t lane;
-	__device__ uint32_t find_nul(const uint8_t *p, uint32_t from, uint32_t len)
-	{
-		for (uint32_t q = from; q < len; q += 64) {
-			const uint32_t i = q + lane;
-			const uint64_t m = __ballot(i < len && p[i] == 0);
-			if (m) return q + (uint32_t)__builtin_ctzll(m);
-		}
-		return len;
-	}
-	__device__ uint32_t crc32(const uint8_t *p, uint32_t n)
-	{
-		uint32_t lo, hi;
-		nxz_slice(n, 64, lane, &lo, &hi);
-		uint32_t v = nxz_crc_part(p, lo, hi, n);
-		for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
-		return nxz_crc_finish(v, n);
-	}
-};
 
 // what the walk calls at every block header: the checkpoint rule, the entry from lane 0 while there is room
 struct Hook {

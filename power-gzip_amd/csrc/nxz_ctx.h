@@ -1,4 +1,4 @@
-// nxz_ctx.h -- what the host sources of libnxz_engine.so share (nxz_engine.cpp, nxz_batch.cpp, nxz_deflate_host.cpp): the
+// nxz_ctx.h -- what the host sources of libnxz_engine.so share (nxz_engine.cpp, nxz_batch.cpp, nxz_batch_framed.cpp, nxz_deflate_host.cpp): the
 // context, a stream's scratch with its buffer type and the rules for touching it, and a few helpers.  Private: not installed.
 #ifndef NXZ_CTX_H
 #define NXZ_CTX_H
@@ -28,6 +28,12 @@
 
 void set_err(const char *what, hipError_t e);              // the calling thread's nxz_last_error() (nxz_engine.cpp)
 #define HIPCHK(x, fail) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(#x, e_); fail; } } while (0)
+// what a batched call returns for the status `rc` of one of its launches (nxz_launch_*): 0, or -EIO with `what` in nxz_last_error()
+static inline int launched(const char *what, int rc)
+{
+	if (rc) { set_err(what, (hipError_t)rc); return -EIO; }
+	return 0;
+}
 
 // one in-flight single job (nxu_run_job)
 struct Slot {
@@ -270,6 +276,13 @@ struct nxz_dict {
 
 hipError_t stream_create_spread(hipStream_t *s, unsigned turn);   // nxz_engine.cpp
 size_t trim_compress_scratch();                                    // nxz_batch.cpp (nxz_trim)
+// nxz_batch.cpp, for the calls of nxz_batch_framed.cpp that run a raw batch or a kernel of its shape.
+// force: 0 -- the kernel by the batch's size and kind; 1 -- a stream per lane, any block type; 2 -- a stream per wavefront
+int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force);
+int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s);
+// The jobs' indices by falling source length in BUF_ORDER of `s`, queued on `s` (NULL: none to be had, the jobs go as they come).
+// The caller holds the lease until its last launch that reads the order.
+const uint32_t *order_by_length_for(nxz_ctx *c, hipStream_t s, const nxz_batch_job_t *jobs, size_t n);
 static inline uint64_t trace_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 #endif

@@ -188,5 +188,22 @@ int nxz_launch_streams_epilogue(const nxz_stream_job_t *desc, const uint32_t *fi
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }
+
+// exclusive prefix sum across one workgroup of 1024 threads (part: 1024 entries of LDS); returns the thread's start, *total
+__device__ inline uint64_t nxz_block_excl(uint64_t v, uint64_t *part, uint64_t *total)
+{
+	const uint32_t t = threadIdx.x;
+	__syncthreads();
+	part[t] = v;
+	__syncthreads();
+	for (uint32_t d = 1; d < 1024; d <<= 1) {
+		const uint64_t u = t >= d ? part[t - d] : 0;
+		__syncthreads();
+		part[t] += u;
+		__syncthreads();
+	}
+	*total = part[1023];
+	return part[t] - v;
+}
 #endif
 #endif

@@ -1,4 +1,4 @@
-// nxz_frame.h -- zlib (RFC 1950) and gzip (RFC 1952) headers, and the BGZF member check, as plain code that
+// nxz_frame.h -- zlib (RFC 1950) and gzip (RFC 1952) headers and trailers, and the BGZF member check, as plain code that
 // compiles for the device (nxz_frame.hip: a wavefront per header) and for the host (tests/native/frame_host.cpp).
 //
 // The parser reads the header one field at a time and stops at the first fault, in zlib's order of checks
@@ -155,6 +155,34 @@ NXZ_HD inline uint32_t nxz_frame_parse_dict(const uint8_t *p, uint32_t len, int 
 		*use_dict = true;
 	}
 	return st;
+}
+
+// ---- the trailer -------------------------------------------------------------------------------------------------
+NXZ_HD inline uint32_t nxz_frame_trailer_bytes(uint32_t format) { return format == NXZ_FMT_GZIP ? 8u : 4u; }
+
+// What stands behind the deflate data of a job whose header parsed (format, hdr_len) and whose deflate data gave r -- a decode's
+// result, or the size walk's.  The first byte behind the final block is hdr_len + spbc - subc / 8 on every route
+// (oracle/nxz_inflate.c: spbc = the source bytes taken, subc = the bits left behind the final end-of-block); the trailer is read
+// from there a byte at a time.  Returns the status; *end, *check and *isize are the frame's fields, 0 unless the trailer was read.
+// compare_check: hold Adler-32 / CRC-32 against r's (the walk has none to compare: without it nothing is NXZ_FRAME_BAD_CHECK).
+// gzip's ISIZE is held against r->tpbc either way.
+NXZ_HD inline uint32_t nxz_frame_trailer(uint32_t format, uint32_t hdr_len, const nxz_batch_result_t *r, const uint8_t *src, uint32_t src_len,
+					 bool compare_check, uint32_t *end, uint32_t *check, uint32_t *isize)
+{
+	*end = *check = *isize = 0;
+	if (!(r->sfbt & 0x100) || (r->cc != NXZ_CC_OK && r->cc != NXZ_CC_DATA_LENGTH))
+		return r->cc == NXZ_CC_DATA_LENGTH ? NXZ_FRAME_TRUNCATED : NXZ_FRAME_DEFLATE;   // (the source ran out before the final block ended)
+	const uint32_t tl = nxz_frame_trailer_bytes(format);
+	const uint64_t dend = (uint64_t)hdr_len + r->spbc - (r->subc >> 3);
+	if (dend + tl > src_len) return NXZ_FRAME_TRUNCATED;
+	const uint8_t *t = src + dend;
+	*end = (uint32_t)dend + tl;
+	if (tl == 4) {
+		*check = nxz_rd32be(t);
+		return compare_check && *check != r->adler ? NXZ_FRAME_BAD_CHECK : NXZ_FRAME_OK;
+	}
+	*check = nxz_rd32le(t); *isize = nxz_rd32le(t + 4);
+	return compare_check && *check != r->crc ? NXZ_FRAME_BAD_CHECK : *isize != r->tpbc ? NXZ_FRAME_BAD_LENGTH : NXZ_FRAME_OK;
 }
 
 // ---- BGZF: one member with the "BC" subfield at p (left bytes from there on) -------------------------------------

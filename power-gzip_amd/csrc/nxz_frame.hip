@@ -1,15 +1,14 @@
 // nxz_frame.hip -- zlib / gzip framing on the device: the kernels around a raw inflate batch that make it a batch of
 // framed streams (nxz_batch_decompress_framed), and the discovery of the members of a BGZF image (nxz_batch_unpack_gzip).
 //
-// Framed streams (nxz_engine.cpp runs the three steps on the caller's stream, nothing waits for the host):
+// Framed streams (nxz_batch_framed.cpp runs the three steps on the caller's stream, nothing waits for the host):
 //   1. frame_header_kernel, a wavefront a job: nxz_frame.h's parser; writes frames[i] and a DERIVED raw job -- the
 //      deflate bytes alone (src + hdr_len, src_len - hdr_len - trailer), checksums from 0 / 1 -- so that the inflate
 //      routes see exactly what a raw batch holds.  A job whose header fails gets a derived job with no source and no
 //      room (src_len = dst_cap = 0): every route ends it at once and writes nothing.
 //   2. the raw batch (nxz_batch_decompress) on the derived jobs;
-//   3. frame_trailer_kernel, a thread a job: the first byte behind the final block is spbc - subc / 8 on every route
-//      (oracle/nxz_inflate.c: spbc = the source length, subc = the bits left behind the final end-of-block), the
-//      trailer is read from there a byte at a time and compared with the raw result's Adler-32 / CRC-32 and length.
+//   3. frame_trailer_kernel, a thread a job: nxz_frame.h's trailer rule -- the trailer behind the final block is read a
+//      byte at a time and compared with the raw result's Adler-32 / CRC-32 and length.
 //
 // BGZF members: a member header can lie anywhere, and a compressed payload can hold bytes that look like one, so
 // every position that passes nxz_bgzf_member_size is a CANDIDATE and the members are the candidates reachable from
@@ -25,31 +24,10 @@
 #include <hip/hip_runtime.h>
 #include "nxz_device.h"
 #include "nxz_frame.h"
+#include "nxz_frame_wave.h"
+#include "nxz_size.h"
 
 namespace nxzf {
-
-struct WaveOps {
-	uint32_t lane;
-	__device__ uint32_t find_nul(const uint8_t *p, uint32_t from, uint32_t len)
-	{
-		for (uint32_t q = from; q < len; q += 64) {
-			const uint32_t i = q + lane;
-			const uint64_t m = __ballot(i < len && p[i] == 0);
-			if (m) return q + (uint32_t)__builtin_ctzll(m);
-		}
-		return len;
-	}
-	__device__ uint32_t crc32(const uint8_t *p, uint32_t n)
-	{
-		uint32_t lo, hi;
-		nxz_slice(n, 64, lane, &lo, &hi);
-		uint32_t v = nxz_crc_part(p, lo, hi, n);
-		for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
-		return nxz_crc_finish(v, n);
-	}
-};
-
-__device__ inline uint32_t trailer_bytes(uint32_t format) { return format == NXZ_FMT_GZIP ? 8u : 4u; }
 
 // four wavefronts a workgroup, a job each (every lane runs the parser on the same bytes: the name / comment scans and
 // the header CRC are the steps that use them all)
@@ -67,7 +45,7 @@ __device__ __forceinline__ void frame_header_body(int fmt, const nxz_batch_job_t
 	bool use_dict = false;
 	uint32_t st = DICT ? nxz_frame_parse_dict(job.src, job.src_len, fmt, &f, ops, true, dictid, &use_dict) : nxz_frame_parse(job.src, job.src_len, fmt, &f, ops);
 	if (st == NXZ_FRAME_OK && (job.resume || job.hist_len)) st = NXZ_FRAME_BAD_HEADER;
-	if (st == NXZ_FRAME_OK && job.src_len - f.hdr_len < trailer_bytes(f.format)) st = NXZ_FRAME_TRUNCATED;
+	if (st == NXZ_FRAME_OK && job.src_len - f.hdr_len < nxz_frame_trailer_bytes(f.format)) st = NXZ_FRAME_TRUNCATED;
 	f.status = st;
 	if (lane) return;
 	frames[i] = f;
@@ -75,7 +53,7 @@ __device__ __forceinline__ void frame_header_body(int fmt, const nxz_batch_job_t
 	d.src = job.src; d.dst = job.dst; d.in_adler = 1;
 	if (st == NXZ_FRAME_OK) {
 		d.src = job.src + f.hdr_len;
-		d.src_len = job.src_len - f.hdr_len - trailer_bytes(f.format);
+		d.src_len = job.src_len - f.hdr_len - nxz_frame_trailer_bytes(f.format);
 		d.dst_cap = job.dst_cap;
 	}
 	if (DICT && !use_dict) d.reserved = NXZ_JOB_NO_DICT;
@@ -99,30 +77,13 @@ __global__ __launch_bounds__(256) void frame_trailer_kernel(const nxz_batch_job_
 	if (i >= n) return;
 	nxz_batch_frame_t *f = &frames[i];
 	if (f->status != NXZ_FRAME_OK) {
-		nxz_batch_result_t z = {};
-		z.cc = NXZ_CC_INVALID_OP;
-		results[i] = z;
+		results[i] = nxz_size_refused();
 		return;
 	}
 	const nxz_batch_result_t r = results[i];
 	const nxz_batch_job_t job = jobs[i];
-	const uint32_t tl = trailer_bytes(f->format);
-	uint32_t st, end = 0, check = 0, isize = 0;
-	if ((r.sfbt & 0x100) && (r.cc == NXZ_CC_OK || r.cc == NXZ_CC_DATA_LENGTH)) {
-		const uint64_t dend = (uint64_t)f->hdr_len + r.spbc - (r.subc >> 3);
-		if (dend + tl > job.src_len) st = NXZ_FRAME_TRUNCATED;
-		else {
-			const uint8_t *t = job.src + dend;
-			end = (uint32_t)dend + tl;
-			if (tl == 4) {
-				check = nxz_rd32be(t);
-				st = check == r.adler ? NXZ_FRAME_OK : NXZ_FRAME_BAD_CHECK;
-			} else {
-				check = nxz_rd32le(t); isize = nxz_rd32le(t + 4);
-				st = check != r.crc ? NXZ_FRAME_BAD_CHECK : isize != r.tpbc ? NXZ_FRAME_BAD_LENGTH : NXZ_FRAME_OK;
-			}
-		}
-	} else st = r.cc == NXZ_CC_DATA_LENGTH ? NXZ_FRAME_TRUNCATED : NXZ_FRAME_DEFLATE;   // (the source ran out before the final block ended)
+	uint32_t end, check, isize;
+	const uint32_t st = nxz_frame_trailer(f->format, f->hdr_len, &r, job.src, job.src_len, true, &end, &check, &isize);
 	f->status = st; f->end = end; f->check = check; f->isize = isize;
 }
 

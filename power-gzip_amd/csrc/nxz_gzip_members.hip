@@ -8,7 +8,7 @@
 // a WARC-like job of thousands of small members is one wavefront's loop.  Successive members start at any byte: the walk takes its
 // source at any alignment.  LDS is the walk's (tables, stage, code lengths: 6.5 KiB); the parsed header lives in registers.
 //
-// The decode, all on the caller's stream (nxz_batch.cpp queues it, nothing waits for the host):
+// The decode, all on the caller's stream (nxz_batch_framed.cpp queues it, nothing waits for the host):
 //   check_kernel    a thread a record slot: a stored OK record that does not lie inside its job marks the job stale
 //   plan_kernel     one workgroup: per job what nxz_gzm_plan says (TARGET_SPACE / INVALID written to streams[i].status) and the
 //                   exclusive prefix sum of the members to decode
@@ -23,32 +23,11 @@
 #include <stdint.h>
 #include "nxz_device.h"
 #include "nxz_frame.h"
+#include "nxz_frame_wave.h"
 #include "nxz_inflate_walk.h"
 #include "nxz_gzip_members.h"
 
 namespace nxzg {
-
-// nxz_frame.hip's steps of the header parser that use the whole wavefront
-struct WaveOps {
-	uint32_t lane;
-	__device__ uint32_t find_nul(const uint8_t *p, uint32_t from, uint32_t len)
-	{
-		for (uint32_t q = from; q < len; q += 64) {
-			const uint32_t i = q + lane;
-			const uint64_t m = __ballot(i < len && p[i] == 0);
-			if (m) return q + (uint32_t)__builtin_ctzll(m);
-		}
-		return len;
-	}
-	__device__ uint32_t crc32(const uint8_t *p, uint32_t n)
-	{
-		uint32_t lo, hi;
-		nxz_slice(n, 64, lane, &lo, &hi);
-		uint32_t v = nxz_crc_part(p, lo, hi, n);
-		for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
-		return nxz_crc_finish(v, n);
-	}
-};
 
 using nxzi::uni;
 
@@ -145,15 +124,8 @@ __global__ __launch_bounds__(1024) void plan_kernel(const nxz_batch_job_t *__res
 	};
 	uint64_t sum = 0;
 	for (uint32_t i = lo; i < hi; i++) sum += wanted(i);
-	part[t] = sum;
-	__syncthreads();
-	for (uint32_t d = 1; d < 1024; d <<= 1) {
-		const uint64_t v = t >= d ? part[t - d] : 0;
-		__syncthreads();
-		part[t] += v;
-		__syncthreads();
-	}
-	uint64_t o = part[t] - sum;
+	uint64_t tot;
+	uint64_t o = nxz_block_excl(sum, part, &tot);
 	for (uint32_t i = lo; i < hi; i++) {
 		const nxz_gzip_stream_t s = streams[i];
 		const uint32_t w = wanted(i);

@@ -56,10 +56,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void si
 	if (lane == 0) results[jid] = nxz_size_record(&stop, job.src_len);
 }
 
-__device__ inline uint32_t trailer_bytes(uint32_t format) { return format == NXZ_FMT_GZIP ? 8u : 4u; }
-
-// The trailer step of nxz_batch_decompress_size_framed, a thread a job: nxz_frame.hip's frame_trailer_kernel without the comparison
-// of the checksum -- the walk has none to compare.  `check` and `isize` are reported as read; gzip's ISIZE is held against tpbc.
+// The trailer step of nxz_batch_decompress_size_framed, a thread a job: nxz_frame.h's trailer rule, as nxz_frame.hip's
+// frame_trailer_kernel runs it, without the comparison of the checksum -- the walk has none to compare.
 __global__ __launch_bounds__(256) void size_trailer_kernel(const nxz_batch_job_t *__restrict__ jobs, uint32_t n,
 							   nxz_batch_result_t *__restrict__ results, nxz_batch_frame_t *__restrict__ frames)
 {
@@ -72,22 +70,8 @@ __global__ __launch_bounds__(256) void size_trailer_kernel(const nxz_batch_job_t
 	}
 	const nxz_batch_result_t r = results[i];
 	const nxz_batch_job_t job = jobs[i];
-	const uint32_t tl = trailer_bytes(f->format);
-	uint32_t st, end = 0, check = 0, isize = 0;
-	if ((r.sfbt & 0x100) && (r.cc == NXZ_CC_OK || r.cc == NXZ_CC_DATA_LENGTH)) {
-		const uint64_t dend = (uint64_t)f->hdr_len + r.spbc - (r.subc >> 3);
-		if (dend + tl > job.src_len) st = NXZ_FRAME_TRUNCATED;
-		else {
-			const uint8_t *t = job.src + dend;
-			end = (uint32_t)dend + tl;
-			st = NXZ_FRAME_OK;
-			if (tl == 4) check = nxz_rd32be(t);
-			else {
-				check = nxz_rd32le(t); isize = nxz_rd32le(t + 4);
-				if (isize != r.tpbc) st = NXZ_FRAME_BAD_LENGTH;
-			}
-		}
-	} else st = r.cc == NXZ_CC_DATA_LENGTH ? NXZ_FRAME_TRUNCATED : NXZ_FRAME_DEFLATE;   // (the source ran out before the final block ended)
+	uint32_t end, check, isize;
+	const uint32_t st = nxz_frame_trailer(f->format, f->hdr_len, &r, job.src, job.src_len, false, &end, &check, &isize);
 	f->status = st; f->end = end; f->check = check; f->isize = isize;
 }
 

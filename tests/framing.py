@@ -111,6 +111,34 @@ def parse(b, fmt):
     return done(OK)
 
 
+CC_OK, CC_DATA_LENGTH = 0, 3
+SFBT_FINAL_EOB = 0x100
+
+
+def trailer(src, fmt, hdr_len, res, compare_check=True):
+    """(status, end, check, isize) of a framed job whose header is hdr_len bytes of format fmt and whose deflate data gave the raw
+    result res (a dict of cc, sfbt, spbc, subc, tpbc, crc, adler as include/nxz_engine.h describes them).  RFC 1950: four bytes
+    behind the deflate data, Adler-32 of the output, most significant byte first.  RFC 1952: eight bytes, CRC-32 of the output and
+    ISIZE = its length mod 2^32, least significant byte first.  The deflate data ends where the decoder stopped: it took spbc bytes
+    behind the header and left subc bits of them unprocessed, so whole unprocessed bytes belong to what follows.  Without
+    compare_check the checksum is reported and not judged (a size query has no output to sum)."""
+    if not res["sfbt"] & SFBT_FINAL_EOB or res["cc"] not in (CC_OK, CC_DATA_LENGTH):
+        # no final end-of-block: the source ran out (the decoder's "more input" code), or the data is wrong
+        return (TRUNCATED if res["cc"] == CC_DATA_LENGTH else DEFLATE), 0, 0, 0
+    dend = hdr_len + res["spbc"] - res["subc"] // 8
+    size = 8 if fmt == FMT_GZIP else 4
+    t = src[dend:dend + size]
+    if dend + size > len(src):
+        return TRUNCATED, 0, 0, 0
+    if fmt == FMT_GZIP:
+        check, isize = struct.unpack("<II", t)
+        st = BAD_CHECK if compare_check and check != res["crc"] else BAD_LENGTH if isize != res["tpbc"] else OK
+    else:
+        check, isize = struct.unpack(">I", t)[0], 0
+        st = BAD_CHECK if compare_check and check != res["adler"] else OK
+    return st, dend + size, check, isize
+
+
 def bgzf_member(data, level=6, before=b"", after=b"", mtime=0):
     """one BGZF member: FLG = FEXTRA, the BC subfield (BSIZE = member size - 1) between other subfields `before` / `after`"""
     c = zlib.compressobj(level, zlib.DEFLATED, -15)

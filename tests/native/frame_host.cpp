@@ -1,9 +1,11 @@
-// frame_host.cpp -- TEST ONLY.  The engine's zlib / gzip header parser and BGZF member check
+// frame_host.cpp -- TEST ONLY.  The engine's zlib / gzip header parser, trailer rule and BGZF member check
 // (power-gzip_amd/csrc/nxz_frame.h, the code the device runs) compiled for the host.  Reads records from stdin:
 //   u8 kind, u8 fmt, u32 len (little-endian), len bytes
 // kind 0: parse the header (fmt = NXZ_FMT_*) -> "status format hdr_len extra_off extra_len name_off comment_off flg xfl os cinfo mtime dictid"
 // kind 1: BGZF member size at the start -> "size"
 // kind 2: CRC-32 of the bytes, by the 64 slices the device combines -> "crc"
+// kind 3: the trailer rule (fmt = the frame's format, | 0x80: compare the checksum).  The bytes are eight little-endian words -- hdr_len
+//         and the result's cc, sfbt, spbc, subc, tpbc, crc, adler -- and then the job's source -> "status end check isize"
 // Every record's bytes sit in an allocation of exactly their length (run under AddressSanitizer).  The first line is the
 // layout of nxz_batch_frame_t: its size and the offsets of its fields.
 #include <cstddef>
@@ -54,6 +56,16 @@ int main()
 			       f.comment_off, f.flg, f.xfl, f.os, f.cinfo, f.mtime, f.dictid);
 		} else if (h[0] == 1) {
 			printf("%u\n", nxz_bgzf_member_size(p, len));
+		} else if (h[0] == 3) {
+			if (len < 32) return 2;
+			uint32_t w[8];
+			for (int k = 0; k < 8; k++) w[k] = nxz_rd32le(p + 4 * k);
+			nxz_batch_result_t r = {};
+			r.cc = w[1]; r.sfbt = w[2]; r.spbc = w[3]; r.subc = w[4]; r.tpbc = w[5]; r.crc = w[6]; r.adler = w[7];
+			const std::vector<uint8_t> src(buf.begin() + 32, buf.end());   // (an allocation of the source's own length)
+			uint32_t end, check, isize;
+			const uint32_t st = nxz_frame_trailer(h[1] & 0x7f, w[0], &r, src.data(), len - 32, (h[1] & 0x80) != 0, &end, &check, &isize);
+			printf("%u %u %u %u\n", st, end, check, isize);
 		} else {
 			printf("%u\n", ops.crc32(p, len));
 		}

@@ -1,6 +1,7 @@
-"""The engine's zlib / gzip header parser and BGZF member check (power-gzip_amd/csrc/nxz_frame.h -- what the header kernel
-and the BGZF discovery of nxz_frame.hip run on the device) compiled for the host under AddressSanitizer, every input in an
-allocation of exactly its length, against an independent Python reading of RFC 1950 / 1952 (tests/framing.py)."""
+"""The engine's zlib / gzip header parser, trailer rule and BGZF member check (power-gzip_amd/csrc/nxz_frame.h -- what the header
+and trailer kernels of nxz_frame.hip and nxz_inflate_size.hip and the BGZF discovery run on the device) compiled for the host under
+AddressSanitizer, every input in an allocation of exactly its length, against an independent Python reading of RFC 1950 / 1952
+(tests/framing.py)."""
 import gzip
 import os
 import random
@@ -157,3 +158,100 @@ def test_bgzf_member_check(host):
     assert got == [F.bgzf_member_size(b) for b in cases]
     assert got[0] == 28 and all(got[1:6]) and not any(got[6:11]) and got[11] == len(m)
     assert got[12:21] == [0] * 9
+
+
+# ---- the trailer rule (nxz_frame_trailer: the trailer kernels of the framed decode, compare_check on, and of the framed size query, off) ----
+def _raw_result(data, deflate_len, unread_bits=0, **over):
+    """the raw result of a decode that took the deflate data and unread_bits more of the source behind it"""
+    r = {"cc": F.CC_OK, "sfbt": F.SFBT_FINAL_EOB, "spbc": deflate_len + unread_bits // 8, "subc": unread_bits, "tpbc": len(data) & 0xffffffff,
+         "crc": zlib.crc32(data), "adler": zlib.adler32(data)}
+    r.update(over)
+    return r
+
+
+def _trailer_streams():
+    """(format, header length, source up to the trailer, right trailer, data)"""
+    data = b"the trailer stands behind the final block " * 40
+    z = F.zlib_stream(data)
+    g = F.gzip_member(data, flg=F.FNAME, name=b"name.txt")
+    return [(F.FMT_ZLIB, 2, z[:-4], z[-4:], data), (F.FMT_GZIP, len(F.gzip_header(F.FNAME, name=b"name.txt")), g[:-8], g[-8:], data)]
+
+
+def _check_trailers(host, cases):
+    """cases: (format, hdr_len, source, result); the C rule equals framing.trailer's with the comparison on and off, and the
+    answer without the comparison is the answer with it except that nothing is BAD_CHECK.  Returns the answers with it on."""
+    recs = []
+    for fmt, hdr_len, src, r in cases:
+        words = struct.pack("<8I", hdr_len, r["cc"], r["sfbt"], r["spbc"], r["subc"], r["tpbc"], r["crc"], r["adler"])
+        recs += [(3, fmt | 0x80, words + src), (3, fmt, words + src)]
+    _, out = host(recs)
+    on = []
+    for k, (fmt, hdr_len, src, r) in enumerate(cases):
+        got_on, got_off = tuple(out[2 * k]), tuple(out[2 * k + 1])
+        assert got_on == F.trailer(src, fmt, hdr_len, r, True), (fmt, hdr_len, len(src), r)
+        assert got_off == F.trailer(src, fmt, hdr_len, r, False), (fmt, hdr_len, len(src), r)
+        assert got_off[0] != F.BAD_CHECK and got_off[1:] == got_on[1:]
+        if got_on[0] != F.BAD_CHECK:
+            assert got_off[0] == got_on[0]
+        on.append(got_on)
+    return on
+
+
+def test_trailer_right_and_wrong_fields(host):
+    """all fields right; zlib's Adler-32 wrong; gzip's CRC-32 wrong, ISIZE wrong, both wrong (the CRC decides)"""
+    (zf, zh, zs, zt, data), (gf, gh, gs, gt, _) = _trailer_streams()
+    zr, gr = _raw_result(data, len(zs) - zh), _raw_result(data, len(gs) - gh)
+    bad_crc, bad_isize = struct.pack("<I", zlib.crc32(data) ^ 0x10), struct.pack("<I", len(data) + 1)
+    cases = [(zf, zh, zs + zt, zr), (gf, gh, gs + gt, gr),
+             (zf, zh, zs + bytes([zt[0] ^ 1]) + zt[1:], zr),
+             (gf, gh, gs + bad_crc + gt[4:], gr), (gf, gh, gs + gt[:4] + bad_isize, gr), (gf, gh, gs + bad_crc + bad_isize, gr),
+             # bytes behind the trailer are no error
+             (zf, zh, zs + zt + b"more", zr), (gf, gh, gs + gt + gs, gr)]
+    on = _check_trailers(host, cases)
+    assert [o[0] for o in on] == [F.OK, F.OK, F.BAD_CHECK, F.BAD_CHECK, F.BAD_LENGTH, F.BAD_CHECK, F.OK, F.OK]
+    assert on[0] == (F.OK, len(zs) + 4, zlib.adler32(data), 0) and on[1] == (F.OK, len(gs) + 8, zlib.crc32(data), len(data))
+    assert on[5][2:] == (zlib.crc32(data) ^ 0x10, len(data) + 1)          # (reported as read)
+
+
+def test_trailer_cut_at_every_length(host):
+    """the source ends anywhere from the end of the deflate data to one byte short of the trailer: TRUNCATED, nothing reported"""
+    cases = []
+    for fmt, hdr_len, body, t, data in _trailer_streams():
+        r = _raw_result(data, len(body) - hdr_len)
+        cases += [(fmt, hdr_len, body + t[:k], r) for k in range(len(t))]
+    on = _check_trailers(host, cases)
+    assert len(on) == 4 + 8 and all(o == (F.TRUNCATED, 0, 0, 0) for o in on)
+
+
+def test_trailer_behind_unread_source_bits(host):
+    """a route that took more of the source than the deflate data: subc unread bits, the whole bytes among them lie behind dend"""
+    cases = []
+    for fmt, hdr_len, body, t, data in _trailer_streams():
+        for subc in (0, 7, 8, 16, 0xfff8):
+            tail = t + b"\xa5" * max(0, subc // 8 - len(t))               # (the source holds the spbc bytes the route took)
+            cases.append((fmt, hdr_len, body + tail, _raw_result(data, len(body) - hdr_len, subc)))
+            cases.append((fmt, hdr_len, body + t[:-1], _raw_result(data, len(body) - hdr_len, subc)))
+    on = _check_trailers(host, cases)
+    for (fmt, hdr_len, src, r), o in zip(cases[::2], on[::2]):
+        assert o[0] == F.OK and o[1] == hdr_len + r["spbc"] - (r["subc"] >> 3) + (8 if fmt == F.FMT_GZIP else 4)
+    assert all(o == (F.TRUNCATED, 0, 0, 0) for o in on[1::2])
+
+
+def test_trailer_of_failed_and_unfinished_results(host):
+    """no final end-of-block: the decoder's "source ran out" code is TRUNCATED, every other code DEFLATE; with the final
+    end-of-block seen that code goes on to the trailer, an error code does not"""
+    codes = (0, 8, 13, 21, 64, 66, 67, 68, 254)
+    cases = []
+    for fmt, hdr_len, body, t, data in _trailer_streams():
+        n = len(body) - hdr_len
+        cases.append((fmt, hdr_len, body + t, _raw_result(data, n, sfbt=0, cc=F.CC_DATA_LENGTH)))
+        cases += [(fmt, hdr_len, body + t, _raw_result(data, n, sfbt=0, cc=cc)) for cc in codes]
+        cases.append((fmt, hdr_len, body + t, _raw_result(data, n, cc=F.CC_DATA_LENGTH)))
+        cases += [(fmt, hdr_len, body + t, _raw_result(data, n, cc=cc)) for cc in codes[1:]]
+        cases.append((fmt, hdr_len, body + t, _raw_result(data, n, sfbt=F.SFBT_FINAL_EOB | 2 | 0x123 << 16)))   # (other bits of sfbt do not matter)
+    on = _check_trailers(host, cases)
+    per = 1 + len(codes) + 1 + len(codes) - 1 + 1
+    for k in (0, per):
+        st = [o[0] for o in on[k:k + per]]
+        assert st == [F.TRUNCATED] + [F.DEFLATE] * len(codes) + [F.OK] + [F.DEFLATE] * (len(codes) - 1) + [F.OK]
+        assert all(o[1:] == (0, 0, 0) for o in on[k:k + per] if o[0] != F.OK)

@@ -305,6 +305,82 @@ def test_bgzf_unpack_index_and_ranges(eng):
             assert st[i] == M.OK and got[offs[i]:offs[i + 1]].tobytes() == data[b:e], (members, i, b, e)
 
 
+def test_bgzf_and_checkpoint_ranges_take_turns(eng):
+    """nxz_bgzf_read_ranges and nxz_checkpoint_read_ranges share BUF_RNG (the map's arrays) and BUF_RNG_SLOTS (a chunk's slots, jobs,
+    frames and results): on one stream a BGZF image of 3 members, a zlib stream of 200 KiB through its index of 16 KiB spans, an
+    image of 40 members, the zlib stream and the small image again -- the map's arrays grow with the members, the slots with the
+    segments (16 KiB and more of output, and an input slot, where a member has 4 KiB at most), and each call gets what the other
+    left.  NXZ_BGZF_CHUNK=3: every call with more than three members runs several chunks.  Eight ranges a call: an empty one, one
+    inside a member, one over more than three, the ends; every byte against the plain slices."""
+    import bisect
+    import torch
+    import checkpoint_model as CM
+    os.environ["NXZ_BGZF_CHUNK"] = "3"
+    dev = eng.dev
+
+    def on_device(b):
+        host = np.zeros(len(b) + 16, np.uint8)
+        host[:len(b)] = np.frombuffer(b, np.uint8)
+        return torch.from_numpy(host).to(dev)
+
+    def eight(u, n):
+        """u: the uncompressed offsets of the members (or segments), n: the plain length"""
+        L, mid = len(u) - 1, (len(u) - 1) // 2
+        r = [(7, 7), (u[mid] + 5, u[mid] + 105), (u[1] - 1, u[min(5, L)] + 1 if L >= 5 else n), (0, n), (n - 1, n), (0, 1),
+             (u[mid + 1] - 3, min(n, u[mid + 1] + 3)), (u[mid] + 50, u[mid] + 80)]
+        assert all(0 <= b <= e <= n for b, e in r) and (L < 5 or bisect.bisect_right(u, r[2][1] - 1) - bisect.bisect_right(u, r[2][0]) >= 4)
+        return r
+
+    def touched(u, ranges):
+        out = set()
+        for b, e in ranges:
+            if b < e:
+                out |= set(range(bisect.bisect_right(u[:-1], b) - 1, bisect.bisect_right(u[:-1], e - 1)))
+        return len(out)
+
+    def check(what, plain, u, ranges, rc, offs, st, out_len, decoded, got):
+        torch.cuda.synchronize(dev)
+        offs, st, got = offs.cpu().numpy(), st.cpu().numpy(), got.cpu().numpy()
+        assert rc == 0 and out_len == offs[-1] == sum(e - b for b, e in ranges), (what, rc, out_len)
+        assert decoded == touched(u, ranges) and (len(u) - 1 <= 3 or decoded > 3), (what, decoded)
+        for i, (b, e) in enumerate(ranges):
+            assert st[i] == pkg.RANGE_OK and got[offs[i]:offs[i + 1]].tobytes() == plain[b:e], (what, i, b, e)
+
+    images = {}
+    for members in (3, 40):
+        plains = sources(members, 300 + members)
+        assert max(len(p) for p in plains) <= 4096
+        image = b"".join(M.member(p, [1, 6, 9][i % 3]) for i, p in enumerate(plains)) + M.EOF_MARKER
+        t = on_device(image)
+        coff, uoff = eng.bgzf_index(t, len(image), members + 8)
+        assert (coff.cpu().tolist(), uoff.cpu().tolist()) == M.index(image), members
+        images[members] = (b"".join(plains), image, t, coff, uoff)
+    plain = b"".join(make_block(KINDS[k % 3], 65536, seed=40 + k) for k in range(3)) + make_block("alice", 8193, seed=44)
+    stream = CM.deflate(plain, CM.FMT_ZLIB, 6, 1)
+    m = CM.index(stream, CM.FMT_ZLIB, 16384)
+    assert m["plain"] == plain and m["count"] >= 6
+    src, out = on_device(stream), on_device(plain)
+    j = np.zeros(1, pkg.JOB_DTYPE)
+    j[0]["src"], j[0]["src_len"], j[0]["dst"], j[0]["dst_cap"], j[0]["in_adler"] = src.data_ptr(), len(stream), out.data_ptr(), len(plain), 1
+    rc, cbit, cuoff, windows, streams = eng.checkpoint_index(pkg.FMT_ZLIB, eng.to_device(j), 1, 16384, m["count"], windows=True)
+    rec = eng.results_to_host(streams, pkg.CHECKPOINT_STREAM_DTYPE)[0]
+    assert rc == 0 and rec["status"] == pkg.CPS_OK and rec["count"] == m["count"]
+    assert cuoff[0].cpu().tolist() == m["uoff"] and cbit[0].cpu().tolist() == m["cbit"]
+    cbit, cuoff, windows = cbit[0].contiguous(), cuoff[0].contiguous(), windows[0].contiguous()
+
+    for turn in (3, "zlib", 40, "zlib", 3):
+        if turn == "zlib":
+            ranges = eight(m["uoff"], len(plain))
+            r = torch.tensor(np.array(ranges, np.int64), device=dev)
+            check(turn, plain, m["uoff"], ranges, *eng.checkpoint_read_ranges(src, len(stream), cbit, cuoff, windows, r))
+        else:
+            data, image, t, coff, uoff = images[turn]
+            u = M.index(image)[1]
+            ranges = eight(u[:-1], len(data))                            # (the end-of-file member holds nothing)
+            r = torch.tensor(np.array(ranges, np.int64), device=dev)
+            check(turn, data, u[:-1], ranges, *eng.bgzf_read_ranges(t, len(image), coff, uoff, r))
+
+
 def test_stream_teardown(eng):
     """nxz_stream_destroy gives the stream's scratch back and drops its entry; a new stream starts from nothing"""
     caller_tables(eng)
