@@ -756,6 +756,62 @@ int nxz_checkpoint_read_ranges(nxz_ctx_t *ctx, const uint8_t *src, uint64_t src_
 			       uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,   /* NXZ_RANGE_* */
 			       uint64_t *out_len, uint64_t *decoded, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Checkpoints inside blocks: a fine index and range reads through it
+ * ---------------------------------------------------------------------- */
+/* The two calls above cut a stream where whoever compressed it ended a block: a hardware compressor's output, a PNG IDAT or a
+ * short Z_FIXED stream can be ONE block and gets ONE checkpoint, and zlib's own blocks run to hundreds of KiB of output (its Z_FIXED
+ * stream of 64 MiB of text has 377).  These two cut a stream every `span` bytes of output, inside blocks:
+ * a checkpoint stands in front of a TOKEN, and a 16-byte state entry beside cbit / uoff says where in a block that is.  The rules
+ * (power-gzip_amd/csrc/nxz_checkpoint_fine.h, on top of nxz_checkpoint.h's rules 3 - 5, which hold as they stand):
+ *   1. checkpoint 0 is the first block header, state all zero;
+ *   2. tokens are a literal (1 byte), a match (len bytes) and every single byte of a stored block; end-of-block codes and headers
+ *      make no bytes.  With c the uoff of the last checkpoint and u bytes of output in front of a token of n bytes: when
+ *      u + n > c + span a checkpoint stands IN FRONT OF that token -- cbit the bit of src where it starts, uoff = u -- and c = u;
+ *   3. a stored run so splits at exactly c + span bytes: cbit is a byte boundary, rem (1..65535) the bytes of the block to come;
+ *   4. an end-of-block code and the next header between the last token that fits and the one that does not: the checkpoint stands
+ *      behind that header, in the new block, with the new block's state;
+ *   5. span >= 258: a token always fits an empty segment, uoff strictly increases, every segment but the last makes between
+ *      span - 257 and span bytes.
+ * This is where a chain of nxz_batch_decompress jobs with NXZ_JOB_SUSPEND_WHEN_FULL and dst_cap = span suspends. */
+typedef struct nxz_checkpoint_state {   /* DEVICE, 16 bytes, beside cbit / uoff: n * (cp_cap + 1), the sentinel's all zero */
+	uint64_t tbit;     /* dynamic block: the bit of src where the block's table starts (HLIT; header bit + 3), else 0 */
+	uint32_t resume;   /* in_rembytecnt | in_sfbt << 16 as nxz_batch_job_t.resume wants them, WITHOUT in_subc; 0: at a block header.
+			    * in_sfbt: 0x8 | BFINAL stored (with rem), 0xa | BFINAL fixed, 0xc | BFINAL dynamic */
+	uint32_t dhtlen;   /* dynamic block: bits of the table, else 0 */
+} nxz_checkpoint_state_t;
+
+/* nxz_batch_checkpoint_index with the rules above (power-gzip_amd/csrc/nxz_checkpoint_fine.hip: the same single launch, the size
+ * walk with a budget of span bytes a segment), and state[i * (cp_cap + 1) + k] beside cbit / uoff.  The table of a dynamic block
+ * is not copied into the index: its position in src is enough, the source is there at read time.  Everything else -- fmt, the
+ * first member of a gzip job, streams[i] and the NXZ_CPS_* outcomes, cp_cap and the sentinel, windows (the same copy from
+ * jobs[i].dst), the 2^32 - 1 limit, asynchrony -- is that call's.  -EINVAL also for span < 258 and state == NULL with n > 0.
+ * Speed (profiles/r15_checkpoints_fine.txt, MI355X): the index takes 0.97 - 0.98 of the coarse index's time on 64 zlib -6 streams of
+ * 16 MiB; through it a 4 KiB read from the middle of a 64 MiB Z_FIXED stream (zlib's: 377 blocks) takes 3.9 ms against 10.6 ms
+ * through the coarse index, the whole stream 5.1 ms against 11.6 ms; with the same tokens as ONE block, 4.0 ms against 138 ms and
+ * 5.0 ms against 138 ms. */
+int nxz_batch_checkpoint_index_fine(nxz_ctx_t *ctx, int fmt /* RAW, ZLIB, GZIP, AUTO */, const nxz_batch_job_t *jobs, size_t n,
+				    uint64_t span /* >= 258 */, uint32_t cp_cap,
+				    uint64_t *cbit, uint64_t *uoff, nxz_checkpoint_state_t *state,   /* DEVICE, n * (cp_cap + 1) each */
+				    uint8_t *windows,                 /* DEVICE, n * cp_cap * 32768, or NULL */
+				    nxz_checkpoint_stream_t *streams, void *stream);
+
+/* nxz_checkpoint_read_ranges through a fine index: state (DEVICE, nidx entries) is the job's part of what the call above wrote.
+ * A segment's job is the coarse call's with resume = state.resume | in_subc << 20, NXZ_JOB_SUSPEND_WHEN_FULL, a target of exactly
+ * the segment's output and, inside a dynamic block, the table -- bits [tbit, tbit + dhtlen) of src shifted to bit 0 -- in a
+ * nxz_batch_dht_t slot of per-stream scratch that goes to nxz_batch_decompress as dht_io.  The segment's source ends with the byte
+ * that holds cbit[k + 1]; a short token whole inside the real bits behind that boundary does not fit the target and is a place to
+ * suspend (CC 3), a cut token runs out of source (CC 3).  A segment is good as there: CC 0 or CC 3 and exactly its bytes.
+ * The index check adds, per entry: entry 0 has resume 0; resume has bits in 0..19 only; in_sfbt is 0 or 0x8..0xd; stored: rem in
+ * 1..65535 and cbit % 8 == 0, else rem 0; dynamic: 1 <= dhtlen <= 8 * NXZ_DHT_MAXSZ, tbit >= 3, tbit + dhtlen <= cbit, else
+ * tbit = dhtlen = 0 -- a stale or foreign index never makes a kernel read outside src, a window slot or a table slot (-EILSEQ).
+ * A state array of zeros over a coarse index reads exactly what nxz_checkpoint_read_ranges reads.  Everything else is that call's. */
+int nxz_checkpoint_read_ranges_fine(nxz_ctx_t *ctx, const uint8_t *src, uint64_t src_len,
+				    const uint64_t *cbit, const uint64_t *uoff, const nxz_checkpoint_state_t *state, const uint8_t *windows,
+				    uint64_t nidx /* count + 1 */, const nxz_bgzf_range_t *ranges, size_t n,
+				    uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,   /* NXZ_RANGE_* */
+				    uint64_t *out_len, uint64_t *decoded, void *stream);
+
 /* Device memory, pinned host memory, streams and asynchronous copies, for callers that hold
  * host buffers and do not link the HIP runtime themselves.  A stream made here is passed as
  * the `stream` argument of the batch calls; nxz_stream_destroy also releases the per-stream

@@ -4,6 +4,7 @@
 #include <functional>
 #include "nxz_ctx.h"
 #include "nxz_streams.h"
+#include "nxz_checkpoint_fine.h"
 
 // ---------------------------------------------------------------------------
 // Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
@@ -348,13 +349,15 @@ static uint64_t bgzf_chunk_members()
 // holds frame_use[s] from the first kernel to the last wait: BUF_RNG and BUF_RNG_SLOTS are both calls'.
 // ---------------------------------------------------------------------------
 // a chunk's part of BUF_RNG_SLOTS: an output slot (and, where the call stages its inputs, an input slot) per member, all of the
-// largest needed member's size and 16-byte aligned, then the members' jobs, frames and results
+// largest needed member's size and 16-byte aligned, then the members' jobs, frames and results (and, where the call asks for them,
+// a table slot per member)
 struct RangeSlots {
 	uint8_t *islots, *oslots;
 	uint64_t istride, ostride;
 	nxz_batch_job_t *jobs;
 	nxz_batch_frame_t *frames;
 	nxz_batch_result_t *results;
+	nxz_batch_dht_t *dht;
 };
 // what the two calls do differently.  Both callables queue on `s`, report their own failures (launched) and return 0 or the error:
 //   map(ws)                 the map kernels into ws (BUF_RNG): ctl = ws[0..5] as nxz_device.h lists them
@@ -364,6 +367,7 @@ struct RangeSteps {
 	std::function<int(uint8_t *ws)> map;
 	std::function<int(uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl)> chunk;
 	bool input_slots;                 // the chunk stages its inputs: slots of ctl[5] bytes (else none, istride 0)
+	bool dht_slots = false;           // the chunk's jobs resume inside dynamic blocks: a nxz_batch_dht_t a member (else none, NULL)
 	const char *gather_what, *zero_what;
 };
 static int read_ranges_locked(nxz_ctx_t *c, hipStream_t s, const RangeSteps &steps, const uint64_t *uoff, uint64_t L, size_t n, uint8_t *dst,
@@ -391,9 +395,10 @@ static int read_ranges_locked(nxz_ctx_t *c, hipStream_t s, const RangeSteps &ste
 	sl.ostride = stride_of(ctl[4]);
 	sl.istride = steps.input_slots ? stride_of(ctl[5]) : 0;
 	const uint64_t per = std::min(needed, std::min(bgzf_chunk_members(), std::max<uint64_t>(1, (1ull << 30) / std::max(sl.istride, sl.ostride))));
-	const size_t ib = up(per * sl.istride), ob = up(per * sl.ostride), jb = up(per * sizeof(nxz_batch_job_t)), fb = up(per * sizeof(nxz_batch_frame_t));
+	const size_t ib = up(per * sl.istride), ob = up(per * sl.ostride), jb = up(per * sizeof(nxz_batch_job_t)), fb = up(per * sizeof(nxz_batch_frame_t)),
+		     rb = up(per * sizeof(nxz_batch_result_t)), db = steps.dht_slots ? per * sizeof(nxz_batch_dht_t) : 0;
 	uint8_t *const slots = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
-		(void)sc.buf[BUF_RNG_SLOTS].grow(s, ib + ob + jb + fb + per * sizeof(nxz_batch_result_t));
+		(void)sc.buf[BUF_RNG_SLOTS].grow(s, ib + ob + jb + fb + rb + db);
 		return sc.buf[BUF_RNG_SLOTS].p;
 	});
 	if (!slots) return -ENOMEM;
@@ -401,6 +406,7 @@ static int read_ranges_locked(nxz_ctx_t *c, hipStream_t s, const RangeSteps &ste
 	sl.jobs = (nxz_batch_job_t *)(slots + ib + ob);
 	sl.frames = (nxz_batch_frame_t *)(slots + ib + ob + jb);
 	sl.results = (nxz_batch_result_t *)(slots + ib + ob + jb + fb);
+	sl.dht = steps.dht_slots ? (nxz_batch_dht_t *)(slots + ib + ob + jb + fb + rb) : nullptr;
 	for (uint64_t k0 = 0; k0 < needed; k0 += per) {
 		const uint64_t cnt = std::min(per, needed - k0);
 		if ((rc = steps.chunk(ws, k0, cnt, sl)) != 0) return rc;
@@ -492,5 +498,75 @@ extern "C" int nxz_checkpoint_read_ranges(nxz_ctx_t *c, const uint8_t *src, uint
 	};
 	steps.input_slots = true;
 	steps.gather_what = "checkpoint gather launch"; steps.zero_what = "checkpoint zero launch";
+	return read_ranges_locked(c, s, steps, uoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
+}
+
+// ---------------------------------------------------------------------------
+// Checkpoints inside blocks (nxz_checkpoint_fine.hip, the rules in nxz_checkpoint_fine.h): the two calls above with a state entry a
+// checkpoint.  The index is the same single launch; the read is the same driver with a check and a job step of its own.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_checkpoint_index_fine(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
+					       uint64_t *cbit, uint64_t *uoff, nxz_checkpoint_state_t *state, uint8_t *windows,
+					       nxz_checkpoint_stream_t *streams, void *stream)
+{
+	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || !nxz_cpf_span_ok(span) || cp_cap == 0 || n >= (1u << 31) ||
+	    (n && (!jobs || !cbit || !uoff || !state || !streams)))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
+	return launched("fine checkpoint index launch", nxz_launch_checkpoint_index_fine(fmt, jobs, n, span, cp_cap, cbit, uoff, state, windows, streams, order, s));
+}
+
+// The segments' jobs bring NXZ_JOB_SUSPEND_WHEN_FULL, which the stream-per-wavefront kernel honours and the stream-per-lane kernel
+// does not.  A chunk is at most 16 384 jobs (bgzf_chunk_members), a third of what sends a batch to the lane kernel by its size
+// (nxz_batch.cpp), and by default it goes to the workgroup kernel, which hands every job with history or resume state -- and every
+// fresh one whose output does not fit or whose source ends early -- to the wavefront kernel.  The one way to the lane kernel is
+// the tuning knob NXZ_INFLATE_LANES_MIN: with it set these chunks are kept off the lane kernel (force 2).  Force 2 rules out the
+// lane and the workgroup kernel, no more: a chunk of 64 jobs or fewer may still take the cut route (nxz_inflate_cut.hip), as it may
+// with NXZ_INFLATE_WG=0 or NXZ_INFLATE_CUT=1 and no force at all.  That route decodes its pieces without the flag and hands every
+// stream whose pieces do not end as planned -- a target that fills among them -- to the wavefront kernel with the job as it came,
+// flag included; tests/test_gpu_checkpoints_fine.py reads through both knobs.
+static int fine_chunk_route()
+{
+	return getenv("NXZ_INFLATE_LANES_MIN") ? 2 : 0;
+}
+
+extern "C" int nxz_checkpoint_read_ranges_fine(nxz_ctx_t *c, const uint8_t *src, uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff,
+					       const nxz_checkpoint_state_t *state, const uint8_t *windows, uint64_t nidx, const nxz_bgzf_range_t *ranges,
+					       size_t n, uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len,
+					       uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !src || !cbit || !uoff || !state || !offsets || nidx < 2 || nidx > 0xffffffffull || (!windows && nidx > 2) || (n && (!ranges || !status)) ||
+	    n >= (1ull << 31))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t L = nidx - 1;
+	RangeSteps steps;
+	steps.map = [&](uint8_t *ws) {
+		int rc = nxz_launch_range_map_clear(ws, n, L, s);
+		if (!rc) rc = nxz_launch_checkpoint_check_fine(src_len, cbit, uoff, state, L, ws, s);
+		if (!rc) rc = nxz_launch_range_map_ranges(uoff, L, ranges, n, offsets, status, ws, s);
+		if (!rc) rc = nxz_launch_checkpoint_inmax(cbit, uoff, n, L, ws, s);
+		return launched("fine checkpoint map launch", rc);
+	};
+	steps.chunk = [&](uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl) {
+		int rc = nxz_launch_checkpoint_stage(src, cbit, uoff, windows, n, L, ws, k0, cnt, sl.islots, sl.istride, sl.oslots, sl.ostride, sl.jobs, s);
+		if (!rc) rc = nxz_launch_checkpoint_jobs_fine(src, cbit, state, n, L, ws, k0, cnt, sl.jobs, sl.dht, s);
+		if ((rc = launched("fine checkpoint stage launch", rc)) != 0) return rc;
+		if ((rc = batch_decompress(c, sl.jobs, (size_t)cnt, sl.results, sl.dht, s, fine_chunk_route())) != 0) return rc;
+		return launched("fine checkpoint verdict launch", nxz_launch_checkpoint_verdict(uoff, n, L, ws, k0, cnt, sl.results, sl.frames, s));
+	};
+	steps.input_slots = true;
+	steps.dht_slots = true;
+	steps.gather_what = "fine checkpoint gather launch"; steps.zero_what = "fine checkpoint zero launch";
 	return read_ranges_locked(c, s, steps, uoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
 }

@@ -187,11 +187,18 @@ extern "C" int nxz_launch_checkpoint_index(int fmt, const nxz_batch_job_t *jobs,
 {
 	if (!n) return 0;
 	hipLaunchKernelGGL(nxzcp::index_kernel, dim3((unsigned)n), dim3(64), 0, stream, fmt, jobs, order, span, cp_cap, cbit, uoff, windows ? 1 : 0, streams);
-	if (windows) {
-		const uint64_t slots = (uint64_t)n * cp_cap;
-		hipLaunchKernelGGL(nxzcp::window_kernel, dim3((unsigned)(slots < (1u << 20) ? slots : (1u << 20))), dim3(256), 0, stream, jobs, slots, cp_cap, uoff,
-				   streams, windows);
-	}
+	const int rc = (int)hipGetLastError();
+	return rc || !windows ? rc : nxz_launch_checkpoint_windows(jobs, n, cp_cap, uoff, streams, windows, stream);
+}
+
+// the windows of the stored checkpoints of n indexed jobs (behind an index kernel on the same stream: this file's, or nxz_checkpoint_fine.hip's)
+extern "C" int nxz_launch_checkpoint_windows(const nxz_batch_job_t *jobs, size_t n, uint32_t cp_cap, const uint64_t *uoff, const nxz_checkpoint_stream_t *streams,
+					     uint8_t *windows, hipStream_t stream)
+{
+	if (!n) return 0;
+	const uint64_t slots = (uint64_t)n * cp_cap;
+	hipLaunchKernelGGL(nxzcp::window_kernel, dim3((unsigned)(slots < (1u << 20) ? slots : (1u << 20))), dim3(256), 0, stream, jobs, slots, cp_cap, uoff,
+			   streams, windows);
 	return (int)hipGetLastError();
 }
 

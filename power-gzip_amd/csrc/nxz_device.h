@@ -170,6 +170,20 @@ int nxz_launch_checkpoint_stage(const uint8_t *src, const uint64_t *cbit, const 
 				nxz_batch_job_t *jobs, hipStream_t stream);
 int nxz_launch_checkpoint_verdict(const uint64_t *uoff, uint64_t n, uint64_t L, uint8_t *ws, uint64_t k0, uint64_t cnt,
 				  const nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);
+/* (the windows' launch alone, for an index of another kind) */
+int nxz_launch_checkpoint_windows(const nxz_batch_job_t *jobs, size_t n, uint32_t cp_cap, const uint64_t *uoff, const nxz_checkpoint_stream_t *streams,
+				  uint8_t *windows, hipStream_t stream);
+/* nxz_checkpoint_fine.hip: checkpoints inside blocks (nxz_checkpoint_fine.h has the rules).  The index with a state entry beside
+ * cbit / uoff, the windows by nxz_launch_checkpoint_windows.  Of the range read's steps two are its own: check (ws[0]: index or a
+ * state entry faulty) and, behind nxz_launch_checkpoint_stage on the same chunk, jobs (dht[k - k0]: the segment's table for
+ * nxz_batch_decompress's dht_io; the jobs' resume and NXZ_JOB_SUSPEND_WHEN_FULL) */
+int nxz_launch_checkpoint_index_fine(int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+				     nxz_checkpoint_state_t *state, uint8_t *windows, nxz_checkpoint_stream_t *streams, const uint32_t *order,
+				     hipStream_t stream);
+int nxz_launch_checkpoint_check_fine(uint64_t src_len, const uint64_t *cbit, const uint64_t *uoff, const nxz_checkpoint_state_t *state, uint64_t L,
+				     uint8_t *ws, hipStream_t stream);
+int nxz_launch_checkpoint_jobs_fine(const uint8_t *src, const uint64_t *cbit, const nxz_checkpoint_state_t *state, uint64_t n, uint64_t L, uint8_t *ws,
+				    uint64_t k0, uint64_t cnt, nxz_batch_job_t *jobs, nxz_batch_dht_t *dht, hipStream_t stream);
 /* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
  * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
  * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */

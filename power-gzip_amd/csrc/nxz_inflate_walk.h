@@ -53,6 +53,16 @@ __device__ __forceinline__ void chain_by_lane(int lane, const uint32_t tl, uint6
 // every lane) -- unless the caller passes a hook of its own (nxz_checkpoint.hip): nothing
 struct NoHook { __device__ __forceinline__ void operator()(uint64_t, uint32_t) const {} };
 
+// A hook that also cuts between tokens (nxz_checkpoint_fine.hip) declares `static constexpr bool fine` and has two more members:
+//   uint32_t budget(uint32_t cap)    the output the walk may reach before the next cut, never above cap
+//   void cut(uint64_t bit, uint32_t out, uint32_t sfbt, uint32_t rem, uint64_t tpos, uint32_t tbits)
+//                                    a token that starts at `bit` (a stored byte: the byte) does not fit the budget: the output in
+//                                    front of it, the block's sfbt, the stored bytes still to come, where the block's table starts
+//                                    (the bit behind the 3-bit header) and its bits -- both 0 unless the block is dynamic
+// The walk asks for the budget behind every header and every cut.  Without `fine` none of this is compiled: the budget is cap.
+template <class H, class = void> struct cuts_tokens { static constexpr bool value = false; };
+template <class H> struct cuts_tokens<H, decltype((void)H::fine)> { static constexpr bool value = true; };
+
 // The walk over srclen bytes at src for a target of cap bytes (0xffffffff: no limit); hist: how far a distance may reach in front of
 // the output.  stop says where and why it ended (nxz_size.h; produced and, behind the final end-of-block code, subc are set), end_bit
 // the bit of src it stands at -- in 64 bits, where stop.subc is a 32-bit field.  Every lane gets the same answers.
@@ -64,7 +74,23 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 	b.src = src; b.srclen = srclen; b.total_bits = (uint64_t)srclen * 8; b.pos = 0;
 	b.stage_base = 0xffffffffu; b.stage = sm.stage; b.lane = lane;
 
+	constexpr bool FINE = cuts_tokens<Hook>::value;
 	uint32_t out = 0;                          // bytes the tokens so far make: never above cap
+	uint32_t soft = cap;                       // what they may make before the hook cuts (FINE; else cap for good)
+	uint64_t tpos = 0;                         // FINE: the table of the dynamic block in work
+	uint32_t tlen = 0;
+	// a token of len bytes that starts at `bit` fits -- if need be behind a cut in front of it
+	auto fits_or_cut = [&](uint32_t len, uint64_t bit, uint32_t sfbt) __attribute__((always_inline)) -> bool {
+		if (nxz_size_fits(out, len, soft)) return true;
+		if constexpr (FINE) {
+			if (soft < cap) {
+				hook.cut(bit, out, sfbt, 0, tpos, tlen);
+				soft = hook.budget(cap);
+				return nxz_size_fits(out, len, soft);
+			}
+		}
+		return false;
+	};
 	int state = 0;                             // 0 header, 1 stored, 2 coded
 	uint32_t bfinal = 0, btype = 0, rem = 0;
 	bool lit_mode = false;                     // the last multi-token step met literals only
@@ -88,6 +114,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 		if (state == 0) {
 			const uint64_t hdr = b.pos;
 			hook(hdr, out);
+			if constexpr (FINE) { soft = hook.budget(cap); tpos = 0; tlen = 0; }
 			if (!b.have(3)) { stop.sfbt = 0xe; stop.subc = (uint32_t)(b.total_bits - hdr); break; }
 			const uint32_t v = b.peek();
 			bfinal = v & 1; btype = (v >> 1) & 3;
@@ -115,6 +142,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 				build<LBITS>(sm.hl, sm.lens, hlit, lane);
 				build<DBITS>(sm.hd, sm.lens + hlit, hdist, lane);
 				stop.have_dht = 1; stop.dhtbits = tbits;
+				if constexpr (FINE) { tpos = hdr + 3; tlen = tbits; }
 				state = 2;
 			} else { stop.cc = NXZ_CC_INVALID_DHT; break; }
 			lit_mode = false;
@@ -122,7 +150,19 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 			// stored bytes: byte aligned; counted, not read
 			const uint64_t srcleft = (b.total_bits - b.pos) >> 3;
 			const uint32_t n = rem < srcleft ? rem : (uint32_t)srcleft;
-			if (!nxz_size_fits(out, n, cap)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
+			if (!nxz_size_fits(out, n, soft)) {
+				if constexpr (FINE) {
+					if (soft < cap) {                                       // the run splits behind the bytes that fit
+						const uint32_t take = soft - out;
+						out += take; rem -= take;
+						b.pos += (uint64_t)take * 8;
+						hook.cut(b.pos, out, 0x8 | bfinal, rem, 0, 0);
+						soft = hook.budget(cap);
+						continue;
+					}
+				}
+				stop.cc = NXZ_CC_TARGET_SPACE; break;
+			}
 			out += n; rem -= n;
 			b.pos += (uint64_t)n * 8;
 			if (rem) { stop.sfbt = 0x8 | bfinal; stop.subc = (uint32_t)(b.total_bits - b.pos); stop.rem = rem; break; }
@@ -166,7 +206,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 					chain_by_lane(lane, ltl, starts, off);
 					lit_mode = off > 63;
 					const uint32_t cnt = (uint32_t)__builtin_popcountll(starts);
-					if (!cnt || !nxz_size_fits(out, cnt, cap)) { lit_mode = false; continue; }
+					if (!cnt || !nxz_size_fits(out, cnt, soft)) { lit_mode = false; continue; }
 					out += cnt;
 					b.pos += off;
 					continue;
@@ -206,7 +246,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 				// before it (the one-token path says what is wrong).  Once output and history make a window's worth every
 				// distance of the format is legal: a scalar test spares the lanes theirs.
 				const bool reach_all = (uint64_t)out + hist >= NXZ_SIZE_WINDOW;
-				const uint64_t bad = __ballot(isstart && (!nxz_size_fits(out, incl, cap) ||
+				const uint64_t bad = __ballot(isstart && (!nxz_size_fits(out, incl, soft) ||
 									  (!reach_all && !islit && !nxz_size_dist_ok(mdist, (uint64_t)out + (incl - x), hist))));
 				if (bad) {
 					const uint32_t first = (uint32_t)__builtin_ctzll(bad);
@@ -232,7 +272,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 			}
 			b.bb_drop(nb);
 			if (sym < 256) {
-				if (!nxz_size_fits(out, 1, cap)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
+				if (!fits_or_cut(1, sym_start, sfbt)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
 				out++;
 			} else if (sym == 256) {
 				if (bfinal) { stop.final_eob = 1; break; }
@@ -261,7 +301,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 				const uint32_t dist = dbase + ((uint32_t)b.bb & ((1u << eb) - 1));
 				b.bb_drop(eb);
 				if (!nxz_size_dist_ok(dist, out, hist)) { stop.cc = NXZ_CC_INVALID_DIST; break; }
-				if (!nxz_size_fits(out, len, cap)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
+				if (!fits_or_cut(len, sym_start, sfbt)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
 				out += len;
 			}
 		}

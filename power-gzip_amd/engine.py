@@ -67,6 +67,10 @@ CHECKPOINT_STREAM_DTYPE = np.dtype([("status", "<u4"), ("count", "<u4"), ("forma
 assert CHECKPOINT_STREAM_DTYPE.itemsize == 32
 CPS_OK, CPS_STREAM_FAILED, CPS_MORE, CPS_NO_OUTPUT, CPS_INVALID = range(5)
 CHECKPOINT_WINDOW = 32768
+# ... and inside blocks (nxz_batch_checkpoint_index_fine / nxz_checkpoint_read_ranges_fine): the state entry beside cbit / uoff
+CHECKPOINT_STATE_DTYPE = np.dtype([("tbit", "<u8"), ("resume", "<u4"), ("dhtlen", "<u4")])
+assert CHECKPOINT_STATE_DTYPE.itemsize == 16
+CHECKPOINT_SPAN_MIN = 258
 
 
 # jobs[].reserved (include/nxz_engine.h)
@@ -180,6 +184,11 @@ def load_library():
         L.nxz_checkpoint_read_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                                  C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.c_void_p]
+        L.nxz_batch_checkpoint_index_fine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_checkpoint_read_ranges_fine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                                      C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_inflate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -525,6 +534,53 @@ class Engine:
                                                      windows.data_ptr() if windows is not None else None, cbit.numel(), ranges.data_ptr(), n,
                                                      d.data_ptr() if d is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
                                                      C.byref(out_len), C.byref(decoded), self.stream_handle())
+        if dst is None:                  # (a first call for the size; the second call runs the map again)
+            rc = call(None, 0)
+            dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
+            if rc != -errno.E2BIG:
+                return rc, offsets, status[:n], out_len.value, decoded.value, dst
+        rc = call(dst, dst.numel())
+        return rc, offsets, status[:n], out_len.value, decoded.value, dst
+
+    def checkpoint_index_fine(self, fmt, jobs, n, span, cp_cap, windows=False, cbit=None, uoff=None, state=None, streams=None):
+        """nxz_batch_checkpoint_index_fine: checkpoint_index with checkpoints inside blocks, every span (>= 258) bytes of output.
+        Returns (rc, cbit, uoff, state, windows, streams): state a uint8 device tensor of shape (n, (cp_cap + 1) * 16) that holds
+        CHECKPOINT_STATE_DTYPE records beside cbit / uoff; the others as there."""
+        t = self.torch
+        if cbit is None:
+            cbit = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if uoff is None:
+            uoff = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if state is None:
+            state = t.zeros((max(n, 1), (cp_cap + 1) * CHECKPOINT_STATE_DTYPE.itemsize), dtype=t.uint8, device=self.dev)
+        if windows is True:
+            windows = t.zeros((max(n, 1), cp_cap, CHECKPOINT_WINDOW), dtype=t.uint8, device=self.dev)
+        elif windows is False:
+            windows = None
+        if streams is None:
+            streams = t.zeros(max(n, 1) * CHECKPOINT_STREAM_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_checkpoint_index_fine(self.ctx, fmt, jobs.data_ptr() if jobs is not None else None, n, span, cp_cap, cbit.data_ptr(),
+                                                    uoff.data_ptr(), state.data_ptr(), windows.data_ptr() if windows is not None else None,
+                                                    streams.data_ptr(), self.stream_handle())
+        return rc, cbit, uoff, state, windows, streams
+
+    def checkpoint_read_ranges_fine(self, src, length, cbit, uoff, state, windows, ranges, dst=None):
+        """checkpoint_read_ranges through a fine index: state a contiguous uint8 device tensor of count + 1 CHECKPOINT_STATE_DTYPE
+        records (one job's row of what checkpoint_index_fine returned).  Returns (rc, offsets, status, out_len, decoded, dst)."""
+        t = self.torch
+        n = ranges.shape[0]
+        offsets = t.zeros(n + 1, dtype=t.int64, device=self.dev)
+        status = t.zeros(max(n, 1), dtype=t.int32, device=self.dev)
+        out_len, decoded = C.c_uint64(), C.c_uint64()
+        assert cbit.numel() == uoff.numel() and cbit.is_contiguous() and uoff.is_contiguous() and ranges.is_contiguous() and ranges.dtype == t.int64
+        assert state.is_contiguous() and state.dtype == t.uint8 and state.numel() == cbit.numel() * CHECKPOINT_STATE_DTYPE.itemsize
+        assert windows is None or windows.is_contiguous()
+
+        def call(d, cap):
+            return self.L.nxz_checkpoint_read_ranges_fine(self.ctx, src.data_ptr(), length, cbit.data_ptr(), uoff.data_ptr(), state.data_ptr(),
+                                                          windows.data_ptr() if windows is not None else None, cbit.numel(), ranges.data_ptr(), n,
+                                                          d.data_ptr() if d is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
+                                                          C.byref(out_len), C.byref(decoded), self.stream_handle())
         if dst is None:                  # (a first call for the size; the second call runs the map again)
             rc = call(None, 0)
             dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
