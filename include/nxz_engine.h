@@ -277,7 +277,10 @@ int nxz_batch_dhtgen(nxz_ctx_t *ctx, const uint32_t *counts, size_t n, nxz_batch
  * jobs[].resume / hist_len are set): each job inflates until final EOB, end
  * of source or full target (CC 13); result.sfbt/subc report where it
  * stopped.  dht_io (NULL or n slots): in = table to resume inside a dynamic
- * block, out = table in force when the job suspended inside one. */
+ * block, out = table in force when the job suspended inside one.  A job that
+ * resumes inside a dynamic block ((in_sfbt & 0xe) == 0xc) in a batch without
+ * dht_io brings no table: cc = NXZ_CC_INVALID_DHT, tpbc = 0, nothing written,
+ * as for a slot whose table does not parse or is not dhtlen bits long. */
 int nxz_batch_decompress(nxz_ctx_t *ctx,
 			 const nxz_batch_job_t *jobs, size_t n,
 			 nxz_batch_result_t *results,

@@ -136,7 +136,8 @@ int nxo_inflate(const uint8_t *src, size_t srclen, uint8_t *dst, size_t dstcap,
 			htab_build(&hd, codes.d_len, 30);
 		} else if (kind == 6) {          /* 110x dynamic */
 			state = ST_CODED; btype = 2;
-			if (nxo_dht_parse(st->dht, st->dhtlen, &codes) != st->dhtlen) {
+			/* (a job that brings no table: the same verdict, nothing read) */
+			if (!st->dht || nxo_dht_parse(st->dht, st->dhtlen, &codes) != st->dhtlen) {
 				st->err = 68;
 				return st->err;
 			}

@@ -360,6 +360,8 @@ __device__ __forceinline__ void inflate_body(const nxz_batch_job_t *__restrict__
 			state = 2; btype = 2;
 			// re-parse the table handed back by the caller -- or, a piece of a stream that begins at a cut inside a block
 			// whose tables were built for the whole block (in_crc, which such pieces have no use for: which): load them
+			// (a batch without dht_io brings no table: NXZ_CC_INVALID_DHT, nothing written -- dht_io is a kernel argument, the test is scalar)
+			if (!dht_io) { cc = NXZ_CC_INVALID_DHT; goto done; }
 			const nxz_batch_dht_t *t = &dht_io[jid];
 			if (W16 && built && job.in_crc) {
 				load_built(sm, &built[job.in_crc - 1], lane);

@@ -11,6 +11,8 @@ import pytest
 
 import oracle_lib as O
 from datagen import make_block
+from inflate_routes import ROUTES, inflate_route
+from run_job import run_both as _run_both
 
 pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("power-gzip_amd")
@@ -32,36 +34,11 @@ def eng():
     os.environ.pop("NXZ_INFLATE_LANES_MIN", None)
 
 
-@pytest.fixture(params=["wg", "wg-128", "lanes", "lanes-fixed", "waves", "waves-global-window", "waves-by-length", "cut", "cut-3"])
+@pytest.fixture(params=ROUTES)
 def inflate_kernel(request):
-    """the inflate kernels: a stream per workgroup with everything in LDS (what every batch gets; what that kernel does not
-    do it hands to the stream-per-wavefront kernel), the same with pieces of 128 bits; a stream per lane; the same with the fixed-code-only kernel in front (which
-    hands a batch with a dynamic block in it back to the first); a stream per wave with its window in
-    LDS, with the target buffer as its window (what mid-size batches get), and that with the jobs taken
-    in the order of their lengths (what batches of more than one round of wavefronts get); every stream
-    cut inside its first block into up to 32 pieces (what small batches get: nxz_inflate_cut.hip), or 3"""
-    old = os.environ.get("NXZ_INFLATE_LANES_MIN")
-    os.environ["NXZ_INFLATE_LANES_MIN"] = "32" if request.param.startswith("lanes") else "1000000000"
-    os.environ["NXZ_LANES_FIXED"] = "2" if request.param == "lanes-fixed" else "0"
-    os.environ["NXZ_INFLATE_CUT"] = "1" if request.param.startswith("cut") else "0"
-    os.environ["NXZ_INFLATE_WG"] = "1" if request.param.startswith("wg") else "0"
-    if request.param == "wg-128":
-        os.environ["NXZ_WG_PMIN"] = "128"
-    if request.param == "cut-3":
-        os.environ["NXZ_INFLATE_CUT_PIECES"] = "3"
-    if request.param in ("waves-global-window", "waves-by-length"):
-        os.environ["NXZ_INFLATE_LDS_MAX"] = "0"
-    if request.param == "waves-by-length":                  # (the jobs in the order of their lengths, as batches beyond one round of wavefronts go)
-        os.environ["NXZ_INFLATE_ORDER"] = "1"
-    yield request.param
-    os.environ.pop("NXZ_INFLATE_ORDER", None)
-    os.environ.pop("NXZ_INFLATE_WG", None)
-    os.environ.pop("NXZ_WG_PMIN", None)
-    os.environ.pop("NXZ_INFLATE_CUT", None)
-    os.environ.pop("NXZ_INFLATE_CUT_PIECES", None)
-    os.environ["NXZ_INFLATE_LANES_MIN"] = old if old is not None else "32"
-    os.environ.pop("NXZ_INFLATE_LDS_MAX", None)
-    os.environ.pop("NXZ_LANES_FIXED", None)
+    """the inflate kernels, one route of nxz_batch_decompress at a time (tests/inflate_routes.py says which they are)"""
+    with inflate_route(request.param) as route:
+        yield route
 
 
 def pack_blocks(eng, blocks, stride):
@@ -407,23 +384,6 @@ def test_inflate_resume_chain(eng, inflate_kernel):
 # ---------------------------------------------------------------------------
 # the six transport symbols: nxu_run_job on host buffers vs the CPU engine model
 # ---------------------------------------------------------------------------
-def _run_both(eng, handle, setup_kwargs, src_bufs_bytes, dst_sizes):
-    """returns (gpu_job, gpu_dst_bytes, cpu_job, cpu_dst_bytes)"""
-    res = []
-    for which in ("gpu", "cpu"):
-        j = crb.Job()
-        srcs = [C.create_string_buffer(b, len(b)) for b in src_bufs_bytes]
-        dsts = [C.create_string_buffer(n) for n in dst_sizes]
-        j.setup(src_bufs=srcs, dst_bufs=dsts, **setup_kwargs)
-        if which == "gpu":
-            rc = eng.L.nxu_run_job(C.c_void_p(j.addr), C.byref(handle))
-        else:
-            rc = O.lib().nxo_run_job(C.c_void_p(j.addr))
-        assert rc == 0 and j.valid == 1
-        res.append((j, b"".join(d.raw for d in dsts)))
-    return res[0][0], res[0][1], res[1][0], res[1][1]
-
-
 @pytest.fixture(scope="module")
 def handle(eng):
     h = crb.DevHandle()
