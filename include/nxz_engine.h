@@ -725,7 +725,7 @@ typedef struct nxz_checkpoint_stream {   /* DEVICE, 32 bytes, one per job */
  * min(uoff[k], 32768) bytes in front of uoff[k] -- copied to the START of slot i * cp_cap + k from jobs[i].dst, which must hold the
  * stream's decoded output (the caller has just made it with nxz_batch_decompress_framed: the index is the by-product of a decode
  * already done).  dst == NULL or dst_cap < out_len: NXZ_CPS_NO_OUTPUT, the positions are valid, that stream's windows are not
- * written.  With windows == NULL dst is never looked at.  Building windows without the full output is not part of this call.
+ * written.  With windows == NULL dst is never looked at.  Windows without the full output: nxz_batch_checkpoint_build below.
  * jobs, cbit, uoff, windows and streams are DEVICE arrays.  Asynchronous on `stream`: no host wait, no allocation beyond the
  * stream's scratch.  Returns 0 (n == 0 included); -EINVAL (ctx, fmt, span == 0, cp_cap == 0, n >= 2^31, a NULL array with n > 0);
  * -ENODEV in a forked child.
@@ -798,6 +798,38 @@ int nxz_batch_checkpoint_index_fine(nxz_ctx_t *ctx, int fmt /* RAW, ZLIB, GZIP, 
 				    uint64_t *cbit, uint64_t *uoff, nxz_checkpoint_state_t *state,   /* DEVICE, n * (cp_cap + 1) each */
 				    uint8_t *windows,                 /* DEVICE, n * cp_cap * 32768, or NULL */
 				    nxz_checkpoint_stream_t *streams, void *stream);
+
+/* The index AND its windows from the source alone, in ONE pass (power-gzip_amd/csrc/nxz_checkpoint_build.hip; the ring's rules in
+ * nxz_checkpoint_build.h): what zran and indexed_gzip do on a CPU.  The two calls above copy their windows out of jobs[i].dst, which
+ * must hold the whole decoded output; this one never looks at jobs[i].dst or dst_cap.  It is the same walk -- one job per wavefront,
+ * the long jobs first -- with every token applied to a ring of the last 32 KiB of output in LDS (stored runs are read from src), and
+ * the ring is written to a checkpoint's slot where the checkpoint is stored.
+ * state != NULL: cbit, uoff, state and streams[i] are exactly what nxz_batch_checkpoint_index_fine writes for a job whose dst holds the
+ * full output (span >= 258); state == NULL: checkpoints at block headers only, exactly what nxz_batch_checkpoint_index writes (any
+ * span >= 1).  The rules, the sentinel, NXZ_CPS_MORE with the true count (the walk goes on to the end of the stream), NXZ_CPS_STREAM_FAILED
+ * with cc / frame_status, NXZ_CPS_INVALID for resume / hist_len, the first member of a gzip job, the 2^32 - 1 limit and the trailer's
+ * checksum that is not looked at are those calls'.  NXZ_CPS_NO_OUTPUT cannot occur.
+ * windows (DEVICE, n * cp_cap slots of 32768 bytes, required): for every stored checkpoint k of a stream that ends NXZ_CPS_OK or
+ * NXZ_CPS_MORE the first min(uoff[k], 32768) bytes of slot i * cp_cap + k are the bytes of output in front of uoff[k] -- the bytes the
+ * calls above copy.  The rest of the slot and the slots beyond the stored checkpoints are not written.  Of a stream that fails, the
+ * slots of checkpoints passed before the failure may have been written: their contents are unspecified, as its cbit entries are;
+ * nothing outside that job's own cp_cap slots is touched.  src and windows may have any alignment (a 16-byte aligned slot gets
+ * 16-byte stores).
+ * Asynchronous on `stream`: no host wait, no allocation beyond the stream's scratch (the by-length launch order).  Returns 0 (n == 0
+ * included); -EINVAL (ctx, fmt, span == 0, span < 258 with state, cp_cap == 0, n >= 2^31, jobs / cbit / uoff / windows / streams
+ * NULL with n > 0); -ENODEV in a forked child.
+ * Not part of this call: checking the trailer's checksum; indexing one stream in several calls; compressing the windows; parallelism
+ * inside one stream (one job is one wavefront's serial decode, as one job is one wavefront's serial walk above).
+ * Speed (profiles/r17_checkpoint_build.txt, MI355X), against nxz_batch_decompress_framed into a full target plus
+ * nxz_batch_checkpoint_index_fine with windows: 1.71 of that route's time on 64 zlib -6 streams of 16 MiB (897 ms against 525 ms) and
+ * 2.7 on 4096 streams of 1 MiB (233 ms against 87 ms), with 0.32 - 0.36 of its device memory at a span of 64 KiB and 0.04 - 0.09 at
+ * 1 MiB (4096 x 1 MiB: 2.3 GiB against 6.3 GiB, 0.4 GiB against 4.4 GiB).  The decode route is the faster one where its target fits. */
+int nxz_batch_checkpoint_build(nxz_ctx_t *ctx, int fmt /* RAW, ZLIB, GZIP, AUTO */, const nxz_batch_job_t *jobs, size_t n,
+			       uint64_t span, uint32_t cp_cap,
+			       uint64_t *cbit, uint64_t *uoff,        /* DEVICE, n * (cp_cap + 1) each */
+			       nxz_checkpoint_state_t *state,         /* DEVICE, n * (cp_cap + 1), or NULL: checkpoints at block headers only */
+			       uint8_t *windows,                      /* DEVICE, n * cp_cap * 32768: required */
+			       nxz_checkpoint_stream_t *streams, void *stream);
 
 /* nxz_checkpoint_read_ranges through a fine index: state (DEVICE, nidx entries) is the job's part of what the call above wrote.
  * A segment's job is the coarse call's with resume = state.resume | in_subc << 20, NXZ_JOB_SUSPEND_WHEN_FULL, a target of exactly

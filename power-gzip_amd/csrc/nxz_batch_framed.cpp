@@ -452,18 +452,32 @@ extern "C" int nxz_bgzf_read_ranges(nxz_ctx_t *c, const uint8_t *packed, uint64_
 // jobs on the long ones first, the order in this stream's scratch under the lease; the windows' copies go behind it on `s`, and
 // nothing waits for the host.
 // ---------------------------------------------------------------------------
-extern "C" int nxz_batch_checkpoint_index(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
-					  uint64_t *cbit, uint64_t *uoff, uint8_t *windows, nxz_checkpoint_stream_t *streams, void *stream)
+// what the three index calls refuse alike (each adds the arrays and the span of its own)
+static bool index_args_ok(const nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap, const uint64_t *cbit,
+			  const uint64_t *uoff, const nxz_checkpoint_stream_t *streams)
 {
-	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || span == 0 || cp_cap == 0 || n >= (1u << 31) || (n && (!jobs || !cbit || !uoff || !streams)))
-		return -EINVAL;
+	return c && fmt >= NXZ_FMT_RAW && fmt <= NXZ_FMT_AUTO && span != 0 && cp_cap != 0 && n < (1u << 31) && (!n || (jobs && cbit && uoff && streams));
+}
+// ... and how they launch: launch(order, s) under the stream's lease, order NULL (the caller's order) below 128 jobs
+template <class Launch>
+static int index_launch(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, void *stream, const char *what, Launch launch)
+{
 	if (forked_child()) return -ENODEV;
 	if (!n) return 0;
 	(void)hipSetDevice(c->device);
 	hipStream_t s = (hipStream_t)stream;
 	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
-	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
-	return launched("checkpoint index launch", nxz_launch_checkpoint_index(fmt, jobs, n, span, cp_cap, cbit, uoff, windows, streams, order, s));
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;
+	return launched(what, launch(order, s));
+}
+
+extern "C" int nxz_batch_checkpoint_index(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
+					  uint64_t *cbit, uint64_t *uoff, uint8_t *windows, nxz_checkpoint_stream_t *streams, void *stream)
+{
+	if (!index_args_ok(c, fmt, jobs, n, span, cp_cap, cbit, uoff, streams)) return -EINVAL;
+	return index_launch(c, jobs, n, stream, "checkpoint index launch", [&](const uint32_t *order, hipStream_t s) {
+		return nxz_launch_checkpoint_index(fmt, jobs, n, span, cp_cap, cbit, uoff, windows, streams, order, s);
+	});
 }
 
 // Ranges of one stream through its checkpoint index: nxz_bgzf_read_ranges with segments for members.  The map is the index check of
@@ -509,16 +523,22 @@ extern "C" int nxz_batch_checkpoint_index_fine(nxz_ctx_t *c, int fmt, const nxz_
 					       uint64_t *cbit, uint64_t *uoff, nxz_checkpoint_state_t *state, uint8_t *windows,
 					       nxz_checkpoint_stream_t *streams, void *stream)
 {
-	if (!c || fmt < NXZ_FMT_RAW || fmt > NXZ_FMT_AUTO || !nxz_cpf_span_ok(span) || cp_cap == 0 || n >= (1u << 31) ||
-	    (n && (!jobs || !cbit || !uoff || !state || !streams)))
-		return -EINVAL;
-	if (forked_child()) return -ENODEV;
-	if (!n) return 0;
-	(void)hipSetDevice(c->device);
-	hipStream_t s = (hipStream_t)stream;
-	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
-	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
-	return launched("fine checkpoint index launch", nxz_launch_checkpoint_index_fine(fmt, jobs, n, span, cp_cap, cbit, uoff, state, windows, streams, order, s));
+	if (!index_args_ok(c, fmt, jobs, n, span, cp_cap, cbit, uoff, streams) || !nxz_cpf_span_ok(span) || (n && !state)) return -EINVAL;
+	return index_launch(c, jobs, n, stream, "fine checkpoint index launch", [&](const uint32_t *order, hipStream_t s) {
+		return nxz_launch_checkpoint_index_fine(fmt, jobs, n, span, cp_cap, cbit, uoff, state, windows, streams, order, s);
+	});
+}
+
+// The index with its windows from the source alone (nxz_checkpoint_build.hip): the same single launch, the walk with a ring of the
+// last 32 KiB of output.  state NULL: the coarse rule, any span; else the fine rule and its span.  jobs[i].dst is never looked at.
+extern "C" int nxz_batch_checkpoint_build(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap,
+					  uint64_t *cbit, uint64_t *uoff, nxz_checkpoint_state_t *state, uint8_t *windows,
+					  nxz_checkpoint_stream_t *streams, void *stream)
+{
+	if (!index_args_ok(c, fmt, jobs, n, span, cp_cap, cbit, uoff, streams) || (state && !nxz_cpf_span_ok(span)) || (n && !windows)) return -EINVAL;
+	return index_launch(c, jobs, n, stream, "checkpoint build launch", [&](const uint32_t *order, hipStream_t s) {
+		return nxz_launch_checkpoint_build(fmt, jobs, n, span, cp_cap, cbit, uoff, state, windows, streams, order, s);
+	});
 }
 
 // The segments' jobs bring NXZ_JOB_SUSPEND_WHEN_FULL, which the stream-per-wavefront kernel honours and the stream-per-lane kernel

@@ -184,6 +184,12 @@ int nxz_launch_checkpoint_check_fine(uint64_t src_len, const uint64_t *cbit, con
 				     uint8_t *ws, hipStream_t stream);
 int nxz_launch_checkpoint_jobs_fine(const uint8_t *src, const uint64_t *cbit, const nxz_checkpoint_state_t *state, uint64_t n, uint64_t L, uint8_t *ws,
 				    uint64_t k0, uint64_t cnt, nxz_batch_job_t *jobs, nxz_batch_dht_t *dht, hipStream_t stream);
+/* nxz_checkpoint_build.hip: the index with its windows from the source alone (nxz_checkpoint_build.h has the ring's rules): the
+ * walk of the two index kernels with a 32 KiB ring of the output in LDS, dumped to a checkpoint's slot where one is stored.
+ * state NULL: checkpoints at block headers only */
+int nxz_launch_checkpoint_build(int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+				nxz_checkpoint_state_t *state, uint8_t *windows, nxz_checkpoint_stream_t *streams, const uint32_t *order,
+				hipStream_t stream);
 /* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
  * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
  * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */

@@ -1,7 +1,8 @@
 // nxz_inflate_walk.h -- the walk of the output-size queries as a device function: from the first block header of a deflate stream to
 // the place it stops, counting the bytes every token would make (no window, no stores, 64-bit sums, src at any alignment).  Shared by
 // nxz_inflate_size.hip (nxzs::size_kernel: a stream a wavefront) and nxz_gzip_members.hip (nxzg::index_kernel: a wavefront walks
-// member after member of a gzip job).  Like nxz_inflate_decode.h it is written for a workgroup of ONE wavefront.
+// member after member of a gzip job); with a hook, by the checkpoint kernels (nxz_checkpoint.hip, nxz_checkpoint_fine.hip) and -- a hook
+// that is handed the bytes of every token -- by nxz_checkpoint_build.hip.  Like nxz_inflate_decode.h it is written for a workgroup of ONE wavefront.
 #ifndef NXZ_INFLATE_WALK_H
 #define NXZ_INFLATE_WALK_H
 #include <hip/hip_runtime.h>
@@ -63,6 +64,16 @@ struct NoHook { __device__ __forceinline__ void operator()(uint64_t, uint32_t) c
 template <class H, class = void> struct cuts_tokens { static constexpr bool value = false; };
 template <class H> struct cuts_tokens<H, decltype((void)H::fine)> { static constexpr bool value = true; };
 
+// A hook that keeps the output (nxz_checkpoint_build.hip: a ring of the last 32 KiB) declares `static constexpr bool bytes` and
+// receives the bytes of every token, in front of the header or cut call that follows them:
+//   void lit(bool on, uint32_t at, uint32_t sym)                     a lane with `on` set holds the literal of output byte `at`
+//   void match(uint32_t at, uint32_t dist, uint32_t len)             the whole wavefront, the same in every lane: len bytes at `at`
+//                                                                    from dist back (dist < len: the copy feeds on itself)
+//   void stored(uint32_t at, const NXZ_GLOBAL_AS uint8_t *p, uint32_t n)   the whole wavefront: n stored bytes at p are output bytes at `at` on
+// Without `bytes` none of this is compiled: stored runs are counted, not read.
+template <class H, class = void> struct keeps_bytes { static constexpr bool value = false; };
+template <class H> struct keeps_bytes<H, decltype((void)H::bytes)> { static constexpr bool value = true; };
+
 // The walk over srclen bytes at src for a target of cap bytes (0xffffffff: no limit); hist: how far a distance may reach in front of
 // the output.  stop says where and why it ended (nxz_size.h; produced and, behind the final end-of-block code, subc are set), end_bit
 // the bit of src it stands at -- in 64 bits, where stop.subc is a 32-bit field.  Every lane gets the same answers.
@@ -75,6 +86,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 	b.stage_base = 0xffffffffu; b.stage = sm.stage; b.lane = lane;
 
 	constexpr bool FINE = cuts_tokens<Hook>::value;
+	constexpr bool KEEP = keeps_bytes<Hook>::value;
 	uint32_t out = 0;                          // bytes the tokens so far make: never above cap
 	uint32_t soft = cap;                       // what they may make before the hook cuts (FINE; else cap for good)
 	uint64_t tpos = 0;                         // FINE: the table of the dynamic block in work
@@ -147,13 +159,14 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 			} else { stop.cc = NXZ_CC_INVALID_DHT; break; }
 			lit_mode = false;
 		} else if (state == 1) {
-			// stored bytes: byte aligned; counted, not read
+			// stored bytes: byte aligned; counted, not read (KEEP: handed to the hook)
 			const uint64_t srcleft = (b.total_bits - b.pos) >> 3;
 			const uint32_t n = rem < srcleft ? rem : (uint32_t)srcleft;
 			if (!nxz_size_fits(out, n, soft)) {
 				if constexpr (FINE) {
 					if (soft < cap) {                                       // the run splits behind the bytes that fit
 						const uint32_t take = soft - out;
+						if constexpr (KEEP) hook.stored(out, src + (uint32_t)(b.pos >> 3), take);
 						out += take; rem -= take;
 						b.pos += (uint64_t)take * 8;
 						hook.cut(b.pos, out, 0x8 | bfinal, rem, 0, 0);
@@ -163,6 +176,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 				}
 				stop.cc = NXZ_CC_TARGET_SPACE; break;
 			}
+			if constexpr (KEEP) hook.stored(out, src + (uint32_t)(b.pos >> 3), n);
 			out += n; rem -= n;
 			b.pos += (uint64_t)n * 8;
 			if (rem) { stop.sfbt = 0x8 | bfinal; stop.subc = (uint32_t)(b.total_bits - b.pos); stop.rem = rem; break; }
@@ -207,6 +221,8 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 					lit_mode = off > 63;
 					const uint32_t cnt = (uint32_t)__builtin_popcountll(starts);
 					if (!cnt || !nxz_size_fits(out, cnt, soft)) { lit_mode = false; continue; }
+					if constexpr (KEEP)
+						hook.lit((starts >> lane) & 1, out + __builtin_amdgcn_mbcnt_hi((uint32_t)(starts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)starts, 0)), lsym);
 					out += cnt;
 					b.pos += off;
 					continue;
@@ -254,6 +270,25 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 					off = first;
 					if (!starts) break;
 				}
+				if constexpr (KEEP) {
+					// All literals of the step at once, then the matches in chain order (nxz_inflate.hip's order for a window
+					// in LDS).  In a ring a literal written ahead of its turn may land on the byte, nearly 32 KiB back, that a
+					// match in front of it still has to read: such a step (rare) goes token by token.
+					const bool mine = (starts >> lane) & 1;
+					const uint32_t opos = incl - x;
+					const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)(63 - __builtin_clzll(starts)));
+					const uint64_t lits = __ballot(islit);
+					const bool ordered = __ballot(mine && !islit && mdist + total > NXZ_SIZE_WINDOW) != 0;
+					if (!ordered) hook.lit(mine && islit, out + opos, sym);
+					uint64_t mm = ordered ? starts : starts & ~lits;
+					while (mm) {
+						const uint32_t l = (uint32_t)__builtin_ctzll(mm);
+						mm &= mm - 1;
+						if ((lits >> l) & 1) { hook.lit((uint32_t)lane == l, out + opos, sym); continue; }
+						hook.match(out + (uint32_t)__builtin_amdgcn_readlane((int)opos, (int)l), (uint32_t)__builtin_amdgcn_readlane((int)mdist, (int)l),
+							   (uint32_t)__builtin_amdgcn_readlane((int)ob, (int)l));
+					}
+				}
 				out += (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)(63 - __builtin_clzll(starts)));
 				lit_mode = !(starts & ~__ballot(islit));                    // (nothing but literals: the next step may be the short one)
 				b.pos += off;
@@ -273,6 +308,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 			b.bb_drop(nb);
 			if (sym < 256) {
 				if (!fits_or_cut(1, sym_start, sfbt)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
+				if constexpr (KEEP) hook.lit(lane == 0, out, (uint32_t)sym);
 				out++;
 			} else if (sym == 256) {
 				if (bfinal) { stop.final_eob = 1; break; }
@@ -302,6 +338,7 @@ __device__ __forceinline__ void walk(Smem &sm, const NXZ_GLOBAL_AS uint8_t *src,
 				b.bb_drop(eb);
 				if (!nxz_size_dist_ok(dist, out, hist)) { stop.cc = NXZ_CC_INVALID_DIST; break; }
 				if (!fits_or_cut(len, sym_start, sfbt)) { stop.cc = NXZ_CC_TARGET_SPACE; break; }
+				if constexpr (KEEP) hook.match(out, dist, len);
 				out += len;
 			}
 		}

@@ -186,6 +186,8 @@ def load_library():
                                                  C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_batch_checkpoint_index_fine.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_checkpoint_build.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_checkpoint_read_ranges_fine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                                       C.POINTER(C.c_uint64), C.c_void_p]
@@ -562,6 +564,29 @@ class Engine:
         rc = self.L.nxz_batch_checkpoint_index_fine(self.ctx, fmt, jobs.data_ptr() if jobs is not None else None, n, span, cp_cap, cbit.data_ptr(),
                                                     uoff.data_ptr(), state.data_ptr(), windows.data_ptr() if windows is not None else None,
                                                     streams.data_ptr(), self.stream_handle())
+        return rc, cbit, uoff, state, windows, streams
+
+    def checkpoint_build(self, fmt, jobs, n, span, cp_cap, state=True, cbit=None, uoff=None, windows=None, streams=None):
+        """nxz_batch_checkpoint_build: the index AND its windows from the source alone, in one pass -- jobs[i].dst is never looked at.
+        state True (or a tensor to write to): checkpoints inside blocks every span (>= 258) bytes, as checkpoint_index_fine;
+        state None / False: at block headers only, as checkpoint_index.  Returns what checkpoint_index_fine returns:
+        (rc, cbit, uoff, state, windows, streams), state None without states, windows always a tensor of shape (n, cp_cap, 32768)."""
+        t = self.torch
+        if cbit is None:
+            cbit = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if uoff is None:
+            uoff = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if state is True:
+            state = t.zeros((max(n, 1), (cp_cap + 1) * CHECKPOINT_STATE_DTYPE.itemsize), dtype=t.uint8, device=self.dev)
+        elif state is False:
+            state = None
+        if windows is None:
+            windows = t.zeros((max(n, 1), cp_cap, CHECKPOINT_WINDOW), dtype=t.uint8, device=self.dev)
+        if streams is None:
+            streams = t.zeros(max(n, 1) * CHECKPOINT_STREAM_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_checkpoint_build(self.ctx, fmt, jobs.data_ptr() if jobs is not None else None, n, span, cp_cap, cbit.data_ptr(),
+                                               uoff.data_ptr(), state.data_ptr() if state is not None else None, windows.data_ptr(),
+                                               streams.data_ptr(), self.stream_handle())
         return rc, cbit, uoff, state, windows, streams
 
     def checkpoint_read_ranges_fine(self, src, length, cbit, uoff, state, windows, ranges, dst=None):
