@@ -500,7 +500,7 @@ int nxz_batch_decompress_framed_dict(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *
  * nxz_inflate_size.hip, the rules in nxz_size.h) and writes results[i] = what nxz_batch_decompress would write for the same job
  * with a target of dst_cap bytes -- cc, tpbc, tebc, spbc, subc and sfbt, bit 8 of sfbt (final EOB seen) and out_dhtlen in bits
  * 16..27 included; a source that ends before the final block is CC 3 with the suspend fields.  The deviations:
- *   - no checksums, no dst: crc = adler = 0.  dst is never read or written and may be NULL or misaligned; src may have any
+ *   - no checksums, no dst: crc = adler = 0 (with them: nxz_batch_decompress_verify below).  dst is never read or written and may be NULL or misaligned; src may have any
  *     alignment.  No dht_io is written.
  *   - dst_cap is the limit: the walk stops with CC 13 at the token a decode would stop at.  0xffffffff = no limit; a stream of
  *     more than 2^32 - 1 bytes of output then gets CC 13.  On CC 13 and on the error codes 66 / 67 / 68 only cc is specified.
@@ -520,12 +520,50 @@ int nxz_batch_decompress_size(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_
  * nxz_batch_decompress_framed_dict and its DICTID rules: a zlib job that names the dictionary is walked with the dictionary's
  * window as its reach), the size walk on the deflate data, and a trailer step that reads frames[i].check / isize and sets end.
  * Every NXZ_FRAME_* status is decided as in the decoding calls -- except NXZ_FRAME_BAD_CHECK, which cannot be detected without the
- * output: a job that a decode would call BAD_CHECK is reported as it would be if its check were right, that is NXZ_FRAME_OK, or
+ * output (nxz_batch_decompress_verify_framed below makes the output's checksums without a target and does detect it): a job that a decode would call BAD_CHECK is reported as it would be if its check were right, that is NXZ_FRAME_OK, or
  * NXZ_FRAME_BAD_LENGTH when gzip's ISIZE differs from tpbc.  frames[i].check is the trailer's value as read.  jobs[].dst is not
  * touched; resume and hist_len must be 0 (NXZ_FRAME_BAD_HEADER). */
 int nxz_batch_decompress_size_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *dict /* may be NULL */,
 				     const nxz_batch_job_t *jobs, size_t n,
 				     nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Verify: checksums and trailer checks, with no target for the decoded bytes
+ * ---------------------------------------------------------------------- */
+/* `gzip -t` over a batch.  The size walk above with every token applied to a ring of the last 32 KiB of output in LDS, as in
+ * nxz_batch_checkpoint_build below, and the ring checksummed as the output passes through it (power-gzip_amd/csrc/
+ * nxz_inflate_verify.hip, the rules in nxz_verify.h).  results[i] is field for field what nxz_batch_decompress_size writes for the
+ * same job, and
+ *   - crc and adler are the CRC-32 and the Adler-32 of the tpbc bytes the stream makes, continued from in_crc / in_adler as
+ *     nxz_batch_decompress continues them.  Both are made for every job.  They are specified wherever the size call specifies the
+ *     record: cc 0, and cc 3 with the suspend fields; on CC 13 and on the error codes only cc is specified, as there.
+ *   - the hist_len (<= 32768) bytes at src are READ: they are the window that distances reach into.  A job over [window][stream]
+ *     verifies exactly as nxz_batch_decompress decodes it, with hist_len = window.
+ * dst is never read or written and may be NULL; src may have any alignment; dst_cap stays the limit (0xffffffff: none), the
+ * 2^32 - 1 edge and the refusal of resume != 0 are the size call's.  Every array is a DEVICE array.
+ * Asynchronous on `stream`: no host wait, no allocation beyond the stream's scratch.  Returns 0 (n == 0 included); -EINVAL (ctx,
+ * n >= 2^31, jobs / results NULL with n > 0); -ENODEV in a forked child.
+ * Not part of these calls: every member of a multi-member gzip job (the first is verified, frames[i].end tells where a second
+ * starts; nxz_batch_gzip_members_size finds them all); parallelism inside one stream (one job is one wavefront's serial walk, as
+ * in the size and build calls); any change to `nxz_gzip -t`.
+ * Speed (profiles/r18_verify.txt, MI355X), against nxz_batch_decompress_framed into full targets: 23.5 times the decode's time on 64
+ * zlib -6 streams of 16 MiB (953 ms against 41 ms) and 9.3 times on 4096 streams of 1 MiB (366 ms against 39 ms), holding 10 MiB of
+ * device memory against 1102 MiB and 2 MiB against 4096 MiB.  That is 1.9 and 7.7 times the size walk; over the build call's walk plus
+ * ring (898 ms, 235 ms) the checksum passes add 6 % and 36 % of the verify's time -- on 4096 streams part of that is three workgroups
+ * a CU where the build kernel has four.  The decode is by far the faster one where its targets fit. */
+int nxz_batch_decompress_verify(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n,
+				nxz_batch_result_t *results, void *stream);
+
+/* The same for zlib / gzip streams: the header kernel of nxz_batch_decompress_framed (with `dict`, which may be NULL, that of
+ * nxz_batch_decompress_framed_dict and its DICTID rules), the verify walk on the deflate data -- a job that names the dictionary
+ * has the dictionary's inflate window as its window, read from the dictionary's one device copy -- and the decode's own trailer
+ * kernel, comparison included.  results[i] and frames[i] are exactly what nxz_batch_decompress_framed[_dict] writes for the same
+ * jobs with targets large enough: NXZ_FRAME_BAD_CHECK and NXZ_FRAME_BAD_LENGTH are decided in the decode's order, and end, check
+ * and isize match.  jobs[].dst is not touched; resume and hist_len must be 0 (NXZ_FRAME_BAD_HEADER).  -EINVAL also for fmt and
+ * for a dictionary of another device, frames NULL with n > 0. */
+int nxz_batch_decompress_verify_framed(nxz_ctx_t *ctx, int fmt, const nxz_dict_t *dict /* may be NULL */,
+				       const nxz_batch_job_t *jobs, size_t n,
+				       nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream);
 
 /* ------------------------------------------------------------------------
  * Multi-member gzip streams: member index and batch decode
@@ -818,7 +856,7 @@ int nxz_batch_checkpoint_index_fine(nxz_ctx_t *ctx, int fmt /* RAW, ZLIB, GZIP, 
  * Asynchronous on `stream`: no host wait, no allocation beyond the stream's scratch (the by-length launch order).  Returns 0 (n == 0
  * included); -EINVAL (ctx, fmt, span == 0, span < 258 with state, cp_cap == 0, n >= 2^31, jobs / cbit / uoff / windows / streams
  * NULL with n > 0); -ENODEV in a forked child.
- * Not part of this call: checking the trailer's checksum; indexing one stream in several calls; compressing the windows; parallelism
+ * Not part of this call: checking the trailer's checksum (nxz_batch_decompress_verify_framed does, also without a target); indexing one stream in several calls; compressing the windows; parallelism
  * inside one stream (one job is one wavefront's serial decode, as one job is one wavefront's serial walk above).
  * Speed (profiles/r17_checkpoint_build.txt, MI355X), against nxz_batch_decompress_framed into a full target plus
  * nxz_batch_checkpoint_index_fine with windows: 1.71 of that route's time on 64 zlib -6 streams of 16 MiB (897 ms against 525 ms) and

@@ -105,6 +105,43 @@ extern "C" int nxz_batch_decompress_size_framed(nxz_ctx_t *c, int fmt, const nxz
 }
 
 // ---------------------------------------------------------------------------
+// Verify (nxz_inflate_verify.hip, the rules in nxz_verify.h): the size calls with the output passing through a ring in LDS and
+// checksummed there -- the same single launch, the same order, the same lease; the framed call ends with the decode's own trailer
+// kernel, comparison included.  A dictionary's window is read from its one device copy.
+// ---------------------------------------------------------------------------
+static int batch_verify(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const nxz_dict *dict, hipStream_t s)
+{
+	const auto use = lease_scratch(c, s);                                // (the kernel reads the order)
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;   // (NULL: in the caller's order)
+	return launched("inflate verify launch", nxz_launch_inflate_verify(jobs, n, results, order, dict ? dict->d_win : nullptr, dict ? dict->win : 0, s));
+}
+
+extern "C" int nxz_batch_decompress_verify(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, void *stream)
+{
+	if (!c || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	return batch_verify(c, jobs, n, results, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int nxz_batch_decompress_verify_framed(nxz_ctx_t *c, int fmt, const nxz_dict_t *dict, const nxz_batch_job_t *jobs, size_t n,
+						  nxz_batch_result_t *results, nxz_batch_frame_t *frames, void *stream)
+{
+	if (!c || (dict && dict->device != c->device) || fmt < NXZ_FMT_ZLIB || fmt > NXZ_FMT_AUTO || n >= (1u << 31) || (n && (!jobs || !results || !frames))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	nxz_batch_job_t *derived = nullptr;
+	int rc = derive_framed_jobs(c, fmt, dict, jobs, n, frames, s, &derived);
+	if (rc) return rc;
+	if ((rc = batch_verify(c, derived, n, results, dict, s)) != 0) return rc;
+	return launched("frame trailer launch", nxz_launch_frame_trailer(jobs, n, results, frames, s));
+}
+
+// ---------------------------------------------------------------------------
 // Multi-member gzip jobs (nxz_gzip_members.hip, the rules in nxz_gzip_members.h).  The index is the size query's shape: a wavefront
 // a job, from 128 jobs on the long ones first, the order in this stream's scratch under the lease.  The decode holds frame_use[s]
 // from its first kernel to its last -- BUF_GZIP_MEMBERS is the framed batch framed_locked works on -- and never waits for the host.

@@ -5,10 +5,9 @@
 //
 //   build_kernel     nxzcp::index_kernel's shape -- one job per wavefront, one wavefront per workgroup, the long jobs first, the
 //                    header by nxz_frame.h's parser, then nxzs::walk.  The hook applies every token to a ring of 32 KiB in LDS
-//                    (literals a lane each, a match by the whole wavefront: all its loads, then all its stores, so that a copy
-//                    that feeds on itself or lies across the wrap reads what stood there before; stored runs from src, four
-//                    bytes a lane) and, where a checkpoint is stored, lane 0 writes cbit / uoff / state and the wavefront dumps
-//                    the ring to the checkpoint's slot: min(uoff, 32768) bytes, oldest first, 16 bytes a lane where the slot's
+//                    (nxz_ring_wave.h's writers, shared with nxz_inflate_verify.hip) and, where a checkpoint is stored, lane 0
+//                    writes cbit / uoff / state and the wavefront dumps the ring to the checkpoint's slot: min(uoff, 32768)
+//                    bytes, oldest first, 16 bytes a lane where the slot's
 //                    alignment allows (LDS is read in aligned dwords and shifted into place).  state == NULL: checkpoints at
 //                    block headers only (nxz_checkpoint.h's rule 2), the budget is never below the cap and nothing is cut.
 //                    LDS is the walk's 6704 bytes and the ring: four workgroups a CU.  The accumulator lives in scalar registers.
@@ -20,12 +19,11 @@
 #include "nxz_inflate_walk.h"
 #include "nxz_checkpoint_fine.h"
 #include "nxz_checkpoint_build.h"
+#include "nxz_ring_wave.h"
 
 namespace nxzcb {
 
 using nxzi::uni;
-
-typedef uint32_t u32_any __attribute__((aligned(1)));
 
 // ring [rs, rs + len) -> d[0, len): the 16-byte granules that lie whole inside d by 16-byte stores, the bytes in front and behind one
 // by one (nxzcp::copy_any with LDS for a source: five aligned dwords a granule, shifted by the ring position's low bits)
@@ -45,73 +43,17 @@ __device__ __forceinline__ void ring_out(const uint32_t *ring, uint32_t rs, uint
 	for (uint32_t i = head + 16 * body + lane; i < len; i += 64) d[i] = rb[rs + i];
 }
 
-// p[0, len) -> ring [rs, rs + len) (no wrap inside): the dwords that lie whole inside the piece by dword stores (the loads at whatever
-// alignment p has: device memory takes them), the bytes in front and behind one by one
-__device__ __forceinline__ void ring_in(uint32_t *ring, uint32_t rs, uint32_t len, const NXZ_GLOBAL_AS uint8_t *p, int lane)
-{
-	uint8_t *const rb = (uint8_t *)ring;
-	uint32_t head = (4 - (rs & 3)) & 3;
-	if (head > len) head = len;
-	const uint32_t body = (len - head) >> 2;
-	if ((uint32_t)lane < head) rb[rs + lane] = p[lane];
-	for (uint32_t g = lane; g < body; g += 64) ring[((rs + head) >> 2) + g] = *(const NXZ_GLOBAL_AS u32_any *)(p + head + 4 * g);
-	const uint32_t done = head + 4 * body;
-	if (done + (uint32_t)lane < len) rb[rs + done + lane] = p[done + lane];
-}
-
 // what the walk calls: at every block header, for its budget, in front of every token that does not fit it -- and with the bytes
 // of every token
-struct Hook {
+struct Hook : nxzr::Writer {             // (the bytes: lit / match / stored into the ring)
 	static constexpr bool fine = true;
 	static constexpr bool bytes = true;
-	uint32_t *ring;
 	nxz_cp_acc_t *acc;
 	uint64_t *cbit, *uoff;
 	nxz_checkpoint_state_t *state;       // NULL: checkpoints at block headers only
 	uint8_t *slots;                      // the job's cp_cap window slots
 	uint64_t span;
 	uint32_t cp_cap, hdr_len;
-	int lane;
-
-	// ---- the bytes ----
-	__device__ __forceinline__ void lit(bool on, uint32_t at, uint32_t sym) const
-	{
-		if (on) ((uint8_t *)ring)[nxz_cb_ring_pos(at)] = (uint8_t)sym;
-	}
-	// a lane a byte, five rounds at most (len <= 258): every source byte lies in front of `at`, and all loads go before the first store
-	__device__ __forceinline__ void match(uint32_t at, uint32_t dist, uint32_t len) const
-	{
-		at = uni(at); dist = uni(dist); len = uni(len);
-		uint8_t *const rb = (uint8_t *)ring;
-		const bool self = dist < len;
-		const uint32_t m = self ? nxz_cb_recip(dist) : 0;
-		if (len <= 64) {
-			const uint32_t i = self ? nxz_cb_mod((uint32_t)lane, dist, m) : (uint32_t)lane;
-			const uint32_t v = (uint32_t)lane < len ? rb[nxz_cb_ring_pos(at - dist + i)] : 0;
-			if ((uint32_t)lane < len) rb[nxz_cb_ring_pos(at + lane)] = (uint8_t)v;
-			return;
-		}
-		uint32_t v[5];
-#pragma unroll
-		for (int k = 0; k < 5; k++) {
-			const uint32_t i = lane + 64 * k;
-			const uint32_t r = self ? nxz_cb_mod(i, dist, m) : i;
-			v[k] = (k < 2 || len > 64u * k) && i < len ? rb[nxz_cb_ring_pos(at - dist + r)] : 0;
-		}
-#pragma unroll
-		for (int k = 0; k < 5; k++) {
-			const uint32_t i = lane + 64 * k;
-			if ((k < 2 || len > 64u * k) && i < len) rb[nxz_cb_ring_pos(at + i)] = (uint8_t)v[k];
-		}
-	}
-	// (a run longer than the ring leaves its last 32 KiB)
-	__device__ __forceinline__ void stored(uint32_t at, const NXZ_GLOBAL_AS uint8_t *p, uint32_t n) const
-	{
-		const uint32_t skip = (uint32_t)nxz_cb_run_skip(uni(n));
-		const nxz_cb_pieces_t r = nxz_cb_run((uint64_t)uni(at) + skip, uni(n) - skip);
-		ring_in(ring, r.start[0], r.len[0], p + skip, lane);
-		if (r.len[1]) ring_in(ring, r.start[1], r.len[1], p + skip + r.len[0], lane);
-	}
 
 	// ---- the checkpoints ----
 	__device__ __forceinline__ void store(uint64_t bit, uint32_t u, const nxz_checkpoint_state_t &s) const
@@ -170,7 +112,7 @@ __global__ __launch_bounds__(64) void build_kernel(int fmt, const nxz_batch_job_
 	uint64_t end_bit = 0;
 	if (st == NXZ_FRAME_OK)
 		nxzs::walk(sm, (const NXZ_GLOBAL_AS uint8_t *)job.src + hdr_len, src_len - hdr_len, 0xffffffffu, 0, lane, stop, end_bit,
-			   Hook{ring, &acc, cb, uo, sta, windows + (size_t)jid * cp_cap * NXZ_CP_WINDOW, span, cp_cap, hdr_len, lane});
+			   Hook{{ring, lane}, &acc, cb, uo, sta, windows + (size_t)jid * cp_cap * NXZ_CP_WINDOW, span, cp_cap, hdr_len});
 	const uint32_t produced = uni(stop.produced);
 	// (the windows are written already: no output is asked for, NXZ_CPS_NO_OUTPUT cannot occur)
 	const nxz_checkpoint_stream_t s = nxz_cp_summary(&acc, cp_cap, format, hdr_len, st, uni(stop.cc), uni(stop.final_eob), produced, false, false);

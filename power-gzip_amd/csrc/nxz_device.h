@@ -145,6 +145,11 @@ int nxz_launch_frame_header_dict(int fmt, const nxz_batch_job_t *jobs, size_t n,
 int nxz_launch_inflate_size(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const uint32_t *order,
 			    uint32_t dict_window, hipStream_t stream);
 int nxz_launch_size_trailer(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t stream);   /* nxz_launch_frame_trailer without the checksum comparison */
+/* nxz_inflate_verify.hip: the same walk with the output passing through a 32 KiB ring in LDS that is checksummed on the way
+ * (nxz_verify.h has the rules): the size record with crc and adler.  dwin: NULL, or a shared dictionary's 32 KiB image whose last
+ * dlen bytes are its inflate window -- the window of every job that does not say NXZ_JOB_NO_DICT */
+int nxz_launch_inflate_verify(const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, const uint32_t *order,
+			      const uint8_t *dwin, uint32_t dlen, hipStream_t stream);
 /* nxz_gzip_members.hip: multi-member gzip jobs (nxz_gzip_members.h has the rules).  The index: a wavefront a job, member after member
  * inside the kernel.  The decode: expand (records checked, the plan, the members as framed jobs in ws: nxz_gzip_members_workspace
  * bytes) -> the framed decode of *xjobs -> join (the verdicts back into members and streams) */

@@ -2,7 +2,7 @@
 // the place it stops, counting the bytes every token would make (no window, no stores, 64-bit sums, src at any alignment).  Shared by
 // nxz_inflate_size.hip (nxzs::size_kernel: a stream a wavefront) and nxz_gzip_members.hip (nxzg::index_kernel: a wavefront walks
 // member after member of a gzip job); with a hook, by the checkpoint kernels (nxz_checkpoint.hip, nxz_checkpoint_fine.hip) and -- a hook
-// that is handed the bytes of every token -- by nxz_checkpoint_build.hip.  Like nxz_inflate_decode.h it is written for a workgroup of ONE wavefront.
+// that is handed the bytes of every token -- by nxz_checkpoint_build.hip and nxz_inflate_verify.hip.  Like nxz_inflate_decode.h it is written for a workgroup of ONE wavefront.
 #ifndef NXZ_INFLATE_WALK_H
 #define NXZ_INFLATE_WALK_H
 #include <hip/hip_runtime.h>

@@ -166,6 +166,10 @@ def load_library():
         L.nxz_batch_decompress_size.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.nxz_batch_decompress_size_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        # ... and their checksums and trailer checks
+        L.nxz_batch_decompress_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_batch_decompress_verify_framed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]
         L.nxz_deflate_stream_bound.restype = C.c_size_t
         L.nxz_batch_gzip_members_size.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_gzip_members_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -382,6 +386,30 @@ class Engine:
         rc = self.L.nxz_batch_decompress_size_framed(self.ctx, fmt, d.handle if d is not None else None, jobs.data_ptr(), n,
                                                      results.data_ptr(), frames.data_ptr(), self.stream_handle())
         self._check(rc, "nxz_batch_decompress_size_framed")
+        return results, frames
+
+    # ---- verify: the same walk with the output's checksums, dst never touched ----
+    def decompress_verify(self, jobs, n, results=None):
+        """nxz_batch_decompress_verify: decompress_size's record with crc and adler of the bytes the stream makes, continued from
+        in_crc / in_adler.  jobs[i].dst may be 0; the hist_len bytes at src are read as the window."""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        self._check(self.L.nxz_batch_decompress_verify(self.ctx, jobs.data_ptr(), n, results.data_ptr(), self.stream_handle()),
+                    "nxz_batch_decompress_verify")
+        return results
+
+    def decompress_verify_framed(self, fmt, jobs, n, d=None, results=None, frames=None):
+        """nxz_batch_decompress_verify_framed: what decompress_framed / decompress_framed_dict (d: a Dict or None) reports, FRAME_BAD_CHECK
+        included, without a target.  Returns (results, frames)."""
+        t = self.torch
+        if results is None:
+            results = t.empty(n * RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if frames is None:
+            frames = t.empty(n * FRAME_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_decompress_verify_framed(self.ctx, fmt, d.handle if d is not None else None, jobs.data_ptr(), n,
+                                                       results.data_ptr(), frames.data_ptr(), self.stream_handle())
+        self._check(rc, "nxz_batch_decompress_verify_framed")
         return results, frames
 
     # ---- multi-member gzip jobs: the member index, then every stored member decoded as one framed batch ----
