@@ -684,6 +684,40 @@ int nxz_batch_deflate_streams(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32
 			      const nxz_stream_job_t *jobs /* HOST */, size_t n,
 			      nxz_stream_result_t *results /* DEVICE */, void *stream);
 
+/* The same with ONE preset dictionary for all streams (the device-side deflateSetDictionary for buffers of any length; what
+ * nxz_batch_compress_dict + nxz_batch_pack_zlib_dict do for sources that fit one block).  Everything not named here is as in
+ * nxz_batch_deflate_streams: jobs, results, fc, level, the chunks, asynchrony.
+ * The block plan does not change: H = hist_max rounded as above, B = 65536 - H, block k starts at k * B and, for k >= 1, sees the
+ * H bytes of its own buffer in front of it.  Block 0 sees the last h0 = min(H, len) & ~15 bytes of the dictionary -- the `prev`
+ * rule of nxz_deflate_host_hist, not the dictionary's own deflate window: hist_max bounds this window as it bounds the others
+ * (hist_max 4096 and a dictionary of 32 KiB: its last 4096 bytes).  WITH hist_max < 16 (H == 0) NO BLOCK HAS A WINDOW: the
+ * stream names the dictionary in its header and never refers to it; a caller who wants the dictionary used passes a hist_max
+ * (32768 for all of it).  The deflate data of stream i is byte for byte what nxz_deflate_host_hist(fc, buffer i, final = 1,
+ * hist_max, prev = the dictionary's bytes, prev_len = len) writes; a buffer of length 0 gives 01 00 00 ff ff and blocks = 0.
+ *   NXZ_FMT_RAW    nothing around it
+ *   NXZ_FMT_ZLIB   the six bytes of nxz_batch_pack_zlib_dict in front (78, FLG with FLEVEL from `level` and FDICT, then
+ *                  nxz_dict_id(dict) most significant byte first: the DICTID of the WHOLE dictionary, 1 for an empty one), the
+ *                  Adler-32 of the source alone big-endian behind
+ *   NXZ_FMT_GZIP   -EINVAL: gzip has no dictionary field
+ * The streams inflate with zlib's inflateSetDictionary(the whole dictionary), with nxz_batch_decompress_dict (raw) and with
+ * nxz_batch_decompress_framed_dict (zlib).  dst_cap >= nxz_deflate_stream_bound_dict(src_len, hist_max, fmt) = the plain bound,
+ * and 4 more for zlib (0 for a format that is not taken); the refusals are the plain call's against this bound, and on
+ * NXZ_CC_TARGET_SPACE out_len is this bound.
+ * On the device a stream's first block goes through the LZ77 kernel as a dictionary job (its window read from the dictionary's
+ * one device copy, nothing read below the buffer), every other block as a plain history job: per chunk two LZ77 launches, one
+ * table and one entropy launch, and one small launch that puts the results back in order (power-gzip_amd/csrc/nxz_streams_dict.hip,
+ * the rules in nxz_streams_dict.h).  How many first blocks a chunk holds the host knows from its pass over the streams: no host wait.
+ * Returns as nxz_batch_deflate_streams; -EINVAL also for dict == NULL, a dictionary of another device, NXZ_FMT_GZIP.
+ * Speed (tools/bench_streams_dict.py, profiles/r19_streams_dict.txt; zlib, DHTGEN, hist_max 32768): 65 536 records of 256 B to 4 KiB
+ * with a 32 KiB dictionary 11.5 GiB/s, 0.85 of the rate of nxz_batch_compress_dict + nxz_batch_pack_zlib_dict on the same records
+ * (13.6 GiB/s, the same bytes out) and 0.78 of the compressed bytes of nxz_batch_deflate_streams without the dictionary; 4096 streams
+ * of 1 MiB 69.7 GiB/s, 0.95 of nxz_batch_deflate_streams (73.5): the chunk's LZ77 work ends twice, once per launch. */
+size_t nxz_deflate_stream_bound_dict(uint64_t src_len, uint32_t hist_max, int fmt);
+int nxz_batch_deflate_streams_dict(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32_t hist_max,
+				   const nxz_dict_t *dict,
+				   const nxz_stream_job_t *jobs /* HOST */, size_t n,
+				   nxz_stream_result_t *results /* DEVICE */, void *stream);
+
 /* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */

@@ -76,7 +76,7 @@ extern "C" uint32_t nxz_dict_id(const nxz_dict_t *d) { return d ? d->id : 1; }
 // entropy kernel, chunk after chunk on the caller's stream.
 static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *jobs, size_t n,
 			  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
-			  uint32_t *counts, void *stream, const nxz_dict *dict);
+			  uint32_t *counts, void *stream, const nxz_dict *dict, const uint8_t *win = nullptr, size_t nwin = 0);
 extern "C" int nxz_batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *jobs, size_t n,
 				  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
 				  uint32_t *counts, void *stream)
@@ -92,9 +92,19 @@ extern "C" int nxz_batch_compress_dict(nxz_ctx_t *c, int fc, const nxz_dict_t *d
 	if (!c || !dict || dict->device != c->device || n >= (1u << 31) || (n && (!jobs || !results))) return -EINVAL;
 	return batch_compress(c, fc, jobs, n, dht, ntables, results, counts, stream, dict);
 }
+// ... with a window of the caller's choosing for the first nwin jobs and none but their own for the rest (nxz_batch_deflate_streams_dict:
+// the first blocks of a chunk's streams, then its other blocks).  The DEVICE jobs are as the kernels take them already -- the first
+// nwin as nxz_launch_dict_jobs would write them, hist_len = the window's length -- so nothing is rewritten and no job is refused.
+int batch_compress_windowed(nxz_ctx_t *c, int fc, const uint8_t *win, size_t nwin, const nxz_batch_job_t *jobs, size_t n,
+			    nxz_batch_result_t *results, void *stream)
+{
+	if (!win || nwin > n) return -EINVAL;
+	return batch_compress(c, fc, jobs, n, nullptr, 0, results, nullptr, stream, nullptr, win, nwin);
+}
+// dict: every job gets the dictionary's deflate window (the caller's jobs are rewritten first).  win: jobs [0, nwin) get `win`.
 static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, size_t n,
 			  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
-			  uint32_t *counts, void *stream, const nxz_dict *dict)
+			  uint32_t *counts, void *stream, const nxz_dict *dict, const uint8_t *win, size_t nwin)
 {
 	const nxz_batch_job_t *jobs = ujobs;
 	if (!c || !nxz_fc_is_compress((uint32_t)fc) || (fc & 1) || (fc & ~0x2e)) return -EINVAL;
@@ -167,13 +177,14 @@ static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, si
 		prepared = sc.buf[BUF_PREPARED].as<nxz_dht_prepared_t>();
 		if (int rc = launched("dht prepare launch", nxz_launch_dht_prepare(dht, ntables, prepared, s))) return rc;
 	}
+	if (dict) { win = dict->deflate_window(); nwin = n; }
 	for (size_t off = 0; off < n; off += chunk) {
 		const size_t m = n - off < chunk ? n - off : chunk;
-		uint32_t *jc = nullptr;
-		{
+		const size_t mw = off < nwin ? std::min(m, nwin - off) : 0;      // the chunk's jobs that take `win`: its first mw
+		auto draw = [&]() {
 			std::lock_guard<std::mutex> g(c->mtx);
-			if (c->d_job_counters) jc = c->d_job_counters + (c->next_counter++ % JOB_COUNTERS);
-		}
+			return c->d_job_counters ? c->d_job_counters + (c->next_counter++ % JOB_COUNTERS) : nullptr;
+		};
 		uint32_t *cnt = count ? counts + off * 316 : gen ? sc.d_counts : nullptr;
 		auto stamp = [&]() {
 			if (!c->timing) return;
@@ -188,8 +199,11 @@ static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, si
 		const int mode = fused_gen ? NXZ_LZ77_FUSED_GEN : fused ? NXZ_LZ77_FUSED_FHT : cnt != nullptr;
 		uint8_t *const lz_scratch = fused_gen ? sc.d_fuse : sc.d_tokens;
 		uint32_t *const lz_counts = fused_gen && !count ? nullptr : cnt;
-		int rc = dict ? nxz_launch_lz77_dict(mode, jobs + off, m, lz_scratch, sc.d_cand2, results + off, lz_counts, jc, dict->deflate_window(), s)
-			      : nxz_launch_lz77(mode, jobs + off, m, lz_scratch, sc.d_cand2, results + off, lz_counts, jc, s);
+		// (a launch indexes tokens and counts by the job's place in it; the fused forms' scratch is a workgroup's, not a job's)
+		int rc = mw ? nxz_launch_lz77_dict(mode, jobs + off, mw, lz_scratch, sc.d_cand2, results + off, lz_counts, draw(), win, s) : 0;
+		if (!rc && mw < m)
+			rc = nxz_launch_lz77(mode, jobs + off + mw, m - mw, fused ? lz_scratch : lz_scratch + mw * (size_t)NXZ_TOK_STRIDE, sc.d_cand2,
+					     results + off + mw, lz_counts ? lz_counts + mw * 316 : nullptr, draw(), s);
 		if ((rc = launched("lz77 launch", rc)) != 0) return rc;
 		stamp();
 		if (fused) { stamp(); stamp(); continue; }

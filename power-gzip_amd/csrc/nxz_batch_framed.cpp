@@ -3,7 +3,7 @@
 // one stream per device buffer, BGZF discovery, index and range reads, checkpoint index and range reads.
 #include <functional>
 #include "nxz_ctx.h"
-#include "nxz_streams.h"
+#include "nxz_streams_dict.h"
 #include "nxz_checkpoint_fine.h"
 
 // ---------------------------------------------------------------------------
@@ -196,6 +196,11 @@ extern "C" int nxz_batch_gzip_members_decode(nxz_ctx_t *c, const nxz_batch_job_t
 // event behind each upload); a caller who queues three calls faster than the device takes two uploads meets it, no other.
 // frame_use[s] guards BUF_STREAMS and the staging, as it guards the derived jobs of the framed calls: nxz_batch_compress takes
 // the scratch lease itself.
+// With a dictionary (nxz_batch_deflate_streams_dict; nxz_streams_dict.hip, the rules in nxz_streams_dict.h) the same function runs: the
+// dictionary form's refusals, prologue and epilogue, and -- when block 0 has a window at all, h0 != 0 -- per chunk an expand that
+// also writes the jobs in launch order (the chunk's first blocks, then the rest), the compress batch with the dictionary's last h0
+// bytes as the window of those first blocks, and a gather of the results back into the batch's order.  How many first blocks a
+// chunk holds the host knows from its one pass (nz[]: the streams with blocks in front of each stream): still no host wait.
 // ---------------------------------------------------------------------------
 static uint32_t streams_chunk()
 {
@@ -209,11 +214,17 @@ extern "C" size_t nxz_deflate_stream_bound(uint64_t src_len, uint32_t hist_max, 
 	return (size_t)nxz_streams_bound(src_len, hist_max, fmt);
 }
 
-extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
-					 nxz_stream_result_t *results, void *stream)
+extern "C" size_t nxz_deflate_stream_bound_dict(uint64_t src_len, uint32_t hist_max, int fmt)
 {
-	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !nxz_streams_fmt_ok(fmt) || level < -1 || level > 9 ||
-	    (n && (!jobs || !results))) return -EINVAL;
+	return nxz_streams_dict_fmt_ok(fmt) ? (size_t)nxz_streams_dict_bound(src_len, hist_max, fmt) : 0;
+}
+
+// dict: NULL, or the dictionary form (its device checked by the caller)
+static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_dict *dict, const nxz_stream_job_t *jobs, size_t n,
+			   nxz_stream_result_t *results, void *stream)
+{
+	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !(dict ? nxz_streams_dict_fmt_ok(fmt) : nxz_streams_fmt_ok(fmt)) ||
+	    level < -1 || level > 9 || (n && (!jobs || !results))) return -EINVAL;
 	if (forked_child()) return -ENODEV;
 	if (!n) return 0;
 	if (n >= (1u << 31)) return -E2BIG;
@@ -222,8 +233,12 @@ extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int leve
 	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
 	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max), ns = (uint32_t)n;
 	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-	// what is uploaded: [descriptors][first], the same layout in the staging and in the device buffer
-	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), up_bytes = o_first + (n + 1) * sizeof(uint32_t);
+	// the first block's window, and whether the chunks' first blocks go apart from the rest
+	const uint32_t h0 = dict ? nxz_streams_dict_window(dict->len, hist_max) : 0;
+	const bool split = h0 != 0;
+	// what is uploaded: [descriptors][first]([nz]), the same layout in the staging and in the device buffer
+	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), o_nz = o_first + up((n + 1) * sizeof(uint32_t)),
+		     up_bytes = split ? o_nz + (n + 1) * sizeof(uint32_t) : o_first + (n + 1) * sizeof(uint32_t);
 	// this call's staging: the upload that read it last must have run
 	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
 	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
@@ -240,18 +255,27 @@ extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int leve
 	// one pass over the streams: a refused stream gets no blocks
 	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st.h;
 	uint32_t *const h_first = (uint32_t *)(st.h + o_first);
+	uint32_t *const h_nz = split ? (uint32_t *)(st.h + o_nz) : nullptr;   // the streams with blocks in front of each stream
 	memcpy(h_desc, jobs, n * sizeof(nxz_stream_job_t));
 	uint64_t total = 0;
+	uint32_t with_blocks = 0;
 	for (size_t i = 0; i < n; i++) {
 		h_first[i] = (uint32_t)total;
-		if (!nxz_streams_refusal(&jobs[i], hist_max, fmt)) total += nxz_streams_blocks(jobs[i].src_len, B);
+		if (h_nz) h_nz[i] = with_blocks;
+		const uint64_t before = total;
+		if (!(dict ? nxz_streams_dict_refusal(&jobs[i], hist_max, fmt) : nxz_streams_refusal(&jobs[i], hist_max, fmt)))
+			total += nxz_streams_blocks(jobs[i].src_len, B);
 		if (total >= (1ull << 31)) return -E2BIG;
+		if (total != before) with_blocks++;
 	}
 	h_first[n] = (uint32_t)total;
+	if (h_nz) h_nz[n] = with_blocks;
 	const uint32_t nblk = (uint32_t)total, C = std::min(streams_chunk(), nblk);
 	const size_t o_state = up(up_bytes), o_jobs = o_state + up(n * sizeof(nxz_stream_state_t)), o_res = o_jobs + up((size_t)C * sizeof(nxz_batch_job_t)),
 		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
-		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), d_bytes = o_slots + (size_t)C * NXZ_STREAMS_SLOT;
+		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), o_ljobs = o_slots + up((size_t)C * NXZ_STREAMS_SLOT),
+		     o_lres = o_ljobs + up((size_t)C * sizeof(nxz_batch_job_t)), o_pos = o_lres + up((size_t)C * sizeof(nxz_batch_result_t)),
+		     d_bytes = split ? o_pos + (size_t)C * sizeof(uint32_t) : o_slots + (size_t)C * NXZ_STREAMS_SLOT;
 	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
 		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
 		return r.buf[BUF_STREAMS].p;
@@ -265,10 +289,15 @@ extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int leve
 	uint32_t *const d_owner = (uint32_t *)(d + o_owner);
 	uint64_t *const d_off = (uint64_t *)(d + o_off);
 	uint8_t *const d_slots = d + o_slots;
+	const uint32_t *const d_nz = split ? (const uint32_t *)(d + o_nz) : nullptr;
+	nxz_batch_job_t *const d_ljobs = split ? (nxz_batch_job_t *)(d + o_ljobs) : nullptr;
+	nxz_batch_result_t *const d_lres = split ? (nxz_batch_result_t *)(d + o_lres) : nullptr;
+	uint32_t *const d_pos = split ? (uint32_t *)(d + o_pos) : nullptr;
 	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
 	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
 	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
-	int rc = launched("streams prologue launch", nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s));
+	int rc = launched("streams prologue launch", dict ? nxz_launch_streams_dict_prologue(d_desc, ns, hist_max, fmt, level, dict->id, d_state, s)
+							  : nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s));
 	if (rc) return rc;
 	const uint32_t op_block = nxz_crc_shift_op(B);
 	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
@@ -277,15 +306,39 @@ extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int leve
 		while (h_first[i_lo + 1] <= b0) i_lo++;
 		uint32_t i_hi = i_lo;
 		while (h_first[i_hi + 1] < b0 + m) i_hi++;
-		rc = launched("streams expand launch", nxz_launch_streams_expand(d_desc, d_first, ns, b0, m, hist_max, d_slots, d_jobs, d_owner, s));
-		if (rc) return rc;
-		if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
+		if (split) {
+			// the first blocks of streams in front of the chunk, and inside it (i_lo and i_hi have blocks: they own b0 and b0 + m - 1)
+			const uint32_t nz_b0 = nxz_streams_dict_firsts_before(h_nz[i_lo], b0 - h_first[i_lo]), nf = nxz_streams_dict_firsts_before(h_nz[i_hi], 1) - nz_b0;
+			rc = launched("streams expand launch", nxz_launch_streams_dict_expand(d_desc, d_first, d_nz, ns, b0, m, hist_max, h0, nz_b0, nf, d_slots,
+											      d_jobs, d_ljobs, d_owner, d_pos, s));
+			if (rc) return rc;
+			if ((rc = batch_compress_windowed(c, fc | 0x08, dict->d_win + nxz_streams_dict_window_at(h0), nf, d_ljobs, m, d_lres, s)) != 0) return rc;
+			if ((rc = launched("streams gather launch", nxz_launch_streams_dict_gather(d_lres, d_pos, m, d_res, s))) != 0) return rc;
+		} else {
+			rc = launched("streams expand launch", nxz_launch_streams_expand(d_desc, d_first, ns, b0, m, hist_max, d_slots, d_jobs, d_owner, s));
+			if (rc) return rc;
+			if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
+		}
 		rc = nxz_launch_streams_layout(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
 		if (!rc) rc = nxz_launch_streams_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, s);
 		if ((rc = launched("streams pack launch", rc)) != 0) return rc;
 		i_lo = i_hi;
 	}
-	return launched("streams epilogue launch", nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s));
+	return launched("streams epilogue launch", dict ? nxz_launch_streams_dict_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s)
+							: nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s));
+}
+
+extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
+					 nxz_stream_result_t *results, void *stream)
+{
+	return deflate_streams(c, fc, fmt, level, hist_max, nullptr, jobs, n, results, stream);
+}
+
+extern "C" int nxz_batch_deflate_streams_dict(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_dict_t *dict,
+					      const nxz_stream_job_t *jobs, size_t n, nxz_stream_result_t *results, void *stream)
+{
+	if (!c || !dict || dict->device != c->device) return -EINVAL;
+	return deflate_streams(c, fc, fmt, level, hist_max, dict, jobs, n, results, stream);
 }
 
 // The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then

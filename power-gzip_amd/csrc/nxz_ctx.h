@@ -280,6 +280,9 @@ size_t trim_compress_scratch();                                    // nxz_batch.
 // force: 0 -- the kernel by the batch's size and kind; 1 -- a stream per lane, any block type; 2 -- a stream per wavefront
 int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force);
 int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s);
+// a compress batch on DEVICE jobs that are as the kernels take them, the first nwin with `win` (16-byte aligned, hist_len bytes) as their window
+int batch_compress_windowed(nxz_ctx_t *c, int fc, const uint8_t *win, size_t nwin, const nxz_batch_job_t *jobs, size_t n,
+			    nxz_batch_result_t *results, void *stream);
 // The jobs' indices by falling source length in BUF_ORDER of `s`, queued on `s` (NULL: none to be had, the jobs go as they come).
 // The caller holds the lease until its last launch that reads the order.
 const uint32_t *order_by_length_for(nxz_ctx *c, hipStream_t s, const nxz_batch_job_t *jobs, size_t n);

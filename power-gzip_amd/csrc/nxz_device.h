@@ -210,6 +210,19 @@ int nxz_launch_streams_pack(const nxz_stream_job_t *desc, const uint32_t *first,
 			    const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, const uint64_t *offsets, hipStream_t stream);
 int nxz_launch_streams_epilogue(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
 				const nxz_stream_state_t *state, nxz_stream_result_t *results, hipStream_t stream);
+/* nxz_streams_dict.hip: the same with a shared dictionary as the window of every stream's first block (nxz_batch_deflate_streams_dict;
+ * nxz_streams_dict.h has the rules).  nz[n + 1]: the streams with blocks in front of each stream; nz_b0 / nf: the first blocks of
+ * streams in front of / inside the chunk; ljobs and lresults: the chunk in launch order (its nf first blocks, then the rest), pos[t]:
+ * block t's place there */
+int nxz_launch_streams_dict_prologue(const nxz_stream_job_t *desc, uint32_t n, uint32_t hist_max, int fmt, int level, uint32_t dictid,
+				     nxz_stream_state_t *state, hipStream_t stream);
+int nxz_launch_streams_dict_expand(const nxz_stream_job_t *desc, const uint32_t *first, const uint32_t *nz, uint32_t n, uint32_t b0,
+				   uint32_t m, uint32_t hist_max, uint32_t h0, uint32_t nz_b0, uint32_t nf, uint8_t *slots,
+				   nxz_batch_job_t *jobs, nxz_batch_job_t *ljobs, uint32_t *owner, uint32_t *pos, hipStream_t stream);
+int nxz_launch_streams_dict_gather(const nxz_batch_result_t *lresults, const uint32_t *pos, uint32_t m, nxz_batch_result_t *results,
+				   hipStream_t stream);
+int nxz_launch_streams_dict_epilogue(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
+				     const nxz_stream_state_t *state, nxz_stream_result_t *results, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

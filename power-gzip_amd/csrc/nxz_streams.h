@@ -95,11 +95,16 @@ NXZ_STREAMS_HD inline uint64_t nxz_streams_bound(uint64_t src_len, uint32_t hist
 }
 
 /* ---- refusals: 0, or the completion code of a stream that is not taken (its dst stays untouched, it gets no blocks) ---- */
-NXZ_STREAMS_HD inline uint32_t nxz_streams_refusal(const nxz_stream_job_t *j, uint32_t hist_max, int fmt)
+/* ... against a bound the caller has worked out (nxz_streams_dict.h has another) */
+NXZ_STREAMS_HD inline uint32_t nxz_streams_refusal_at(const nxz_stream_job_t *j, uint64_t bound)
 {
 	if ((!j->src && j->src_len) || ((uintptr_t)j->src & 15) || !j->dst) return NXZ_CC_INVALID_OP;
-	if (j->dst_cap < nxz_streams_bound(j->src_len, hist_max, fmt)) return NXZ_CC_TARGET_SPACE;
+	if (j->dst_cap < bound) return NXZ_CC_TARGET_SPACE;
 	return 0;
+}
+NXZ_STREAMS_HD inline uint32_t nxz_streams_refusal(const nxz_stream_job_t *j, uint32_t hist_max, int fmt)
+{
+	return nxz_streams_refusal_at(j, nxz_streams_bound(j->src_len, hist_max, fmt));
 }
 
 /* ---- CRC-32 of [a][b] from those of a and b ---- */

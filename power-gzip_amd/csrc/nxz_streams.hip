@@ -1,6 +1,6 @@
 // nxz_streams.hip -- the kernels around the compress batch of nxz_batch_deflate_streams (include/nxz_engine.h): a batch of device
 // buffers of any length, each written as ONE raw, zlib or gzip stream.  The rules (block plan, bound, framing, checksum joins) are
-// nxz_streams.h; a block is laid into its stream by pack_block (nxz_pack_block.h), as nxz_deflate_host's kernels lay theirs.
+// nxz_streams.h, the steps shared with the dictionary form (nxz_streams_dict.hip) nxz_streams_dev.h; a block is laid into its stream by pack_block (nxz_pack_block.h), as nxz_deflate_host's kernels lay theirs.
 //
 //   prologue   a thread per stream: refusals, the header bytes, the stream's running state
 //   expand     a thread per block of a chunk: whose block it is (upper bound in the streams' block prefix), its compress job
@@ -11,22 +11,10 @@
 //   epilogue   a thread per stream: the empty streams' body, the trailers, results[]
 // A stream is indexed by a uint32_t everywhere (a batch holds fewer than 2^31 streams and blocks).
 #include <hip/hip_runtime.h>
-#include "nxz_device.h"
-#include "nxz_streams.h"
+#include "nxz_streams_dev.h"
 #include "nxz_pack_block.h"
 
 namespace nxzst {
-
-// the stream that block g of the batch belongs to: the i with first[i] <= g < first[i + 1] (streams without blocks are passed over)
-__device__ inline uint32_t owner_of(const uint32_t *__restrict__ first, uint32_t n, uint32_t g)
-{
-	uint32_t lo = 0, hi = n - 1;
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if (first[mid + 1] > g) hi = mid; else lo = mid + 1;
-	}
-	return lo;
-}
 
 __global__ __launch_bounds__(256) void prologue_kernel(const nxz_stream_job_t *__restrict__ desc, uint32_t n, uint32_t hist_max, int fmt, int level,
 							 nxz_stream_state_t *__restrict__ state)
@@ -34,16 +22,9 @@ __global__ __launch_bounds__(256) void prologue_kernel(const nxz_stream_job_t *_
 	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
 	const nxz_stream_job_t j = desc[i];
-	nxz_stream_state_t st;
-	st.cc = nxz_streams_refusal(&j, hist_max, fmt);
-	st.written = 0; st.len_done = 0; st.crc = 0; st.adler = 1; st.stored = 0;
-	if (!st.cc) {
-		uint8_t h[10];
-		const uint32_t hl = nxz_streams_header(fmt, level, h);
-		for (uint32_t k = 0; k < hl; k++) j.dst[k] = h[k];
-		st.written = hl;
-	}
-	state[i] = st;
+	uint8_t h[10];
+	const uint32_t hl = nxz_streams_header(fmt, level, h);
+	state[i] = begin_stream(j, nxz_streams_refusal(&j, hist_max, fmt), h, hl);
 }
 
 __global__ __launch_bounds__(256) void expand_kernel(const nxz_stream_job_t *__restrict__ desc, const uint32_t *__restrict__ first, uint32_t n,
@@ -54,17 +35,7 @@ __global__ __launch_bounds__(256) void expand_kernel(const nxz_stream_job_t *__r
 	if (t >= m) return;
 	const uint32_t g = b0 + t, i = owner_of(first, n, g);
 	const uint64_t k = g - first[i];
-	const nxz_stream_job_t d = desc[i];
-	const uint32_t hk = nxz_streams_block_window(k, B, H);
-	nxz_batch_job_t j;
-	j.src = d.src + nxz_streams_block_start(k, B) - hk;
-	j.dst = slots + (size_t)t * NXZ_STREAMS_SLOT;
-	j.src_len = hk + nxz_streams_block_len(d.src_len, k, B);
-	j.hist_len = hk;
-	j.dst_cap = NXZ_STREAMS_SLOT;
-	j.in_crc = 0; j.in_adler = 1;
-	j.dht_index = 0; j.resume = 0; j.reserved = 0;
-	jobs[t] = j;
+	jobs[t] = block_job(desc[i], k, B, nxz_streams_block_window(k, B, H), slots + (size_t)t * NXZ_STREAMS_SLOT);
 	owner[t] = i;
 }
 
@@ -161,28 +132,7 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const nxz_stream_job_t *_
 	const uint32_t i = blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
 	const nxz_stream_job_t j = desc[i];
-	const nxz_stream_state_t st = state[i];
-	nxz_stream_result_t r;
-	r.cc = st.cc; r.blocks = 0; r.out_len = 0; r.crc = 0; r.adler = 0; r.stored = 0; r.reserved = 0;
-	if (st.cc) {
-		if (st.cc == NXZ_CC_TARGET_SPACE) r.out_len = nxz_streams_bound(j.src_len, hist_max, fmt);
-		results[i] = r;
-		return;
-	}
-	uint64_t at = st.written;
-	if (!j.src_len) {
-		uint8_t e[NXZ_STREAMS_EMPTY_LEN];
-		nxz_streams_empty(e);
-		for (uint32_t k = 0; k < NXZ_STREAMS_EMPTY_LEN; k++) j.dst[at + k] = e[k];
-		at += NXZ_STREAMS_EMPTY_LEN;
-	}
-	uint8_t tr[8];
-	const uint32_t tl = nxz_streams_trailer(fmt, st.crc, st.adler, j.src_len, tr);
-	for (uint32_t k = 0; k < tl; k++) j.dst[at + k] = tr[k];
-	r.blocks = first[i + 1] - first[i];
-	r.out_len = at + tl;
-	r.crc = st.crc; r.adler = st.adler; r.stored = st.stored;
-	results[i] = r;
+	results[i] = finish_stream(j, state[i], first[i + 1] - first[i], nxz_streams_bound(j.src_len, hist_max, fmt), fmt);
 }
 
 } // namespace nxzst

@@ -88,6 +88,12 @@ def dict_deflate_window(n):
     return min(n, DICT_WINDOW) & ~15
 
 
+def stream_dict_window(n, hist_max):
+    """bytes of an n-byte dictionary that block 0 of a deflate_streams_dict stream sees: its last min(H, n) & ~15, H the window of
+    hist_max (nxz_streams_dict.h) -- the `prev` rule of nxz_deflate_host_hist, not dict_deflate_window"""
+    return min(min(hist_max & ~15, 32768), n) & ~15
+
+
 class Dict:
     """nxz_dict_t: a preset dictionary on the device, shared by all jobs of the *_dict calls (Engine.dict_create)"""
 
@@ -177,6 +183,10 @@ def load_library():
         L.nxz_deflate_stream_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
         L.nxz_batch_deflate_streams.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p]
+        L.nxz_deflate_stream_bound_dict.restype = C.c_size_t
+        L.nxz_deflate_stream_bound_dict.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
+        L.nxz_batch_deflate_streams_dict.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -454,17 +464,45 @@ class Engine:
         """bufs: uint8 device tensors (16-byte aligned, any length) -> one stream each (FMT_RAW / FMT_ZLIB / FMT_GZIP).  Returns
         (out, offsets, results): stream i stands at out[offsets[i]:] (a uint8 device tensor with room for every stream's bound),
         results[i].out_len bytes long; results as deflate_stream_jobs.  Asynchronous: results_to_host(results, STREAM_RESULT_DTYPE)."""
+        return self._deflate_streams(fc, fmt, None, bufs, hist_max, level)
+
+    # ---- ... with one preset dictionary as the window of every stream's first block ----
+    def deflate_stream_bound_dict(self, src_len, hist_max=0, fmt=FMT_ZLIB):
+        """nxz_deflate_stream_bound_dict: the dst_cap a buffer of src_len bytes needs (FMT_RAW / FMT_ZLIB; 0 for FMT_GZIP)"""
+        return self.L.nxz_deflate_stream_bound_dict(src_len, hist_max, fmt)
+
+    def deflate_stream_jobs_dict(self, fc, fmt, d, jobs, results=None, hist_max=0, level=-1):
+        """nxz_batch_deflate_streams_dict: as deflate_stream_jobs; d: a Dict (None is passed on as NULL, which the call refuses)"""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, STREAM_JOB_DTYPE)
+        n = len(jobs)
+        if results is None:
+            results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_deflate_streams_dict(self.ctx, fc, fmt, level, hist_max, d.handle if d is not None else None,
+                                                   jobs.ctypes.data if n else None, n, results.data_ptr(), self.stream_handle())
+        return rc, results
+
+    def deflate_streams_dict(self, fc, fmt, d, bufs, hist_max=0, level=-1):
+        """as deflate_streams with the Dict d: block 0 of every stream sees the dictionary's last stream_dict_window(len, hist_max)
+        bytes -- none at hist_max 0, where the stream only names the dictionary (FMT_RAW / FMT_ZLIB)"""
+        return self._deflate_streams(fc, fmt, d, bufs, hist_max, level)
+
+    def _deflate_streams(self, fc, fmt, d, bufs, hist_max, level):
         t = self.torch
         j = np.zeros(len(bufs), STREAM_JOB_DTYPE)
-        caps = [self.deflate_stream_bound(b.numel(), hist_max, fmt) for b in bufs]
+        bound = self.deflate_stream_bound if d is None else self.deflate_stream_bound_dict
+        caps = [bound(b.numel(), hist_max, fmt) for b in bufs]
         offsets = np.zeros(len(bufs) + 1, np.int64)
         offsets[1:] = np.cumsum([(c + 15) & ~15 for c in caps])
         out = t.empty(max(int(offsets[-1]), 1), dtype=t.uint8, device=self.dev)
         for i, b in enumerate(bufs):
             assert b.dtype == t.uint8 and b.is_contiguous() and b.device == out.device
             j[i] = (b.data_ptr() if b.numel() else 0, out.data_ptr() + int(offsets[i]), b.numel(), caps[i])
-        rc, results = self.deflate_stream_jobs(fc, fmt, j, hist_max=hist_max, level=level)
-        self._check(rc, "nxz_batch_deflate_streams")
+        if d is None:
+            rc, results = self.deflate_stream_jobs(fc, fmt, j, hist_max=hist_max, level=level)
+        else:
+            rc, results = self.deflate_stream_jobs_dict(fc, fmt, d, j, hist_max=hist_max, level=level)
+        self._check(rc, "nxz_batch_deflate_streams" if d is None else "nxz_batch_deflate_streams_dict")
         return out, offsets, results
 
     def frames_to_host(self, frames):
