@@ -6,9 +6,10 @@
 // ---------------------------------------------------------------------------
 // batched, device-resident interface
 // ---------------------------------------------------------------------------
-// Jobs per launch of the three compress kernels: bounds the token scratch (104 KiB per job: 832 MiB for 8192
+// Jobs per launch of the compress kernels: bounds the token scratch (104 KiB per job: 832 MiB for 8192
 // jobs, 6.6 GiB for 65536).  Larger chunks cost memory, smaller ones time: the LZ77 kernel is one persistent
-// workgroup per CU, at the end of a launch CUs idle until the last job is done, and every chunk is three launches
+// workgroup per CU, at the end of a launch CUs idle until the last job is done, and every chunk is four launches
+// (LZ77, symbol counts, table, entropy; three for a caller's table or the fixed code with counts)
 // (the corpus, 262144 jobs: 92.8 GiB/s at 8192 jobs per launch, 94.7 at 16384, 95.8 at 32768, 96.4 at 65536).  So the
 // chunk grows with the batch -- a quarter to an eighth of it, 8192 at least and 65536 at most: a caller with a few thousand jobs
 // never pays gigabytes for them -- and falls back to 8192 when the device has no room for more.
@@ -72,8 +73,9 @@ extern "C" void nxz_dict_destroy(nxz_ctx_t *c, nxz_dict_t *d)
 }
 extern "C" uint32_t nxz_dict_id(const nxz_dict_t *d) { return d ? d->id : 1; }
 
-// The compress function codes: LZ77 kernel (tokens, counts, checksums) -> [table generator] ->
-// entropy kernel, chunk after chunk on the caller's stream.
+// The compress function codes: LZ77 kernel (tokens) -> [symbol counts -> table generator] ->
+// entropy kernel (the block, its checksums), chunk after chunk on the caller's stream.  (The symbol-count kernel is
+// nxz_launch_lz77's own second launch: the stage stamps count it as "lz77".)
 static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *jobs, size_t n,
 			  const nxz_batch_dht_t *dht, size_t ntables, nxz_batch_result_t *results,
 			  uint32_t *counts, void *stream, const nxz_dict *dict, const uint8_t *win = nullptr, size_t nwin = 0);
@@ -118,7 +120,7 @@ static int batch_compress(nxz_ctx_t *c, int fc, const nxz_batch_job_t *ujobs, si
 	hipStream_t s = (hipStream_t)stream;   // NULL = the HIP default stream
 	(void)hipSetDevice(c->device);
 	nxz_dht_prepared_t *prepared = nullptr;
-	// equal chunks (a last chunk of a few jobs would cost three launches for nothing)
+	// equal chunks (a last chunk of a few jobs would cost four launches for nothing)
 	// the fixed code without counts: the LZ77 kernel writes the finished block itself (no tokens in device scratch,
 	// no entropy launch, and so no reason to cut the batch into chunks: one launch, one tail)
 	// ... and so it can for the additive DHTGEN function codes (round 5, NXZ_FUSED_GEN=1): the table of a block is made, and the block

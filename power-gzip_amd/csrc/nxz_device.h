@@ -42,6 +42,9 @@ size_t nxz_lz77_cand2_bytes(void);     /* scratch of a launch: the second bucket
 size_t nxz_lz77_gen_scratch_bytes(void);
 int nxz_launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t *tokens, uint16_t *cand2, nxz_batch_result_t *results,
 		    uint32_t *counts, uint32_t *job_counter, hipStream_t stream);
+/* nxz_symcount.hip: counts[i * 316 ..] of jobs[i] from the bitmaps and records at tokens + i * NXZ_TOK_STRIDE and the source.
+ * nxz_launch_lz77 with count == 1 launches it itself, behind the LZ77 kernel's form that does not count */
+int nxz_launch_symcount(const nxz_batch_job_t *jobs, size_t n, const uint8_t *tokens, uint32_t *counts, hipStream_t stream);
 int nxz_launch_encode(int dht, int table_per_job, const nxz_batch_job_t *jobs, size_t n, const uint8_t *tokens,
 		      const nxz_dht_prepared_t *tables, nxz_batch_result_t *results, hipStream_t stream);
 int nxz_launch_dhtgen(const uint32_t *counts, size_t n, nxz_dht_prepared_t *prepared,

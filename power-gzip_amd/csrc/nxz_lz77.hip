@@ -11,8 +11,10 @@
 // this kernel must reproduce that restatement's tokens exactly.  What leaves the kernel
 // (nxz_device.h, NXZ_TOK_*): a bitmap of the positions where a literal token starts, a bitmap of
 // the positions where a match token starts, the (length, distance) records of the matches in
-// parse order, the LZ symbol counts (286 + 30, the COUNT function codes' out_lzcount and the
-// input of the table generator nxz_dhtgen.hip).  The entropy stage (nxz_encode.hip) makes the deflate block from
+// parse order.  The LZ symbol counts (286 + 30, the COUNT function codes' out_lzcount and the
+// input of the table generator nxz_dhtgen.hip) are made from these by nxzsc::count_kernel (nxz_symcount.hip), which
+// launch_lz77 puts behind this kernel; the forms of this kernel that count in their out phase themselves (COUNT) are the
+// fused dynamic form's and NXZ_LZ77_COUNT_INKERNEL=1's.  The entropy stage (nxz_encode.hip) makes the deflate block from
 // them, and the block's checksums from the source: only the forms of this kernel that finish the block themselves
 // (FUSED, GEN -- no entropy launch behind them) have the cksum phase.
 //
@@ -36,11 +38,12 @@
 //            [entry, X[s]) and mark their tokens in the two bitmaps (register masks, one LDS
 //            atomic per lane)
 //     out    lane per 16 positions: match records to the job's record array at the rank a
-//            workgroup prefix sum of the match counts gives; symbol counts by LDS atomics;
-//            the two bitmaps as coalesced dwords
+//            workgroup prefix sum of the match counts gives; the two bitmaps as coalesced dwords;
+//            (COUNT only) symbol counts by LDS atomics
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+#include <stdlib.h>
 #include "nxz_device.h"
 #include "nxz_dhtgen_dev.h"
 #include "nxz_dict.h"
@@ -1974,6 +1977,12 @@ static int launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t
 	// count: 0 tokens for the entropy kernel, 1 tokens + symbol counts, 2 (NXZ_LZ77_FUSED_FHT) the finished fixed-Huffman block,
 	// 3 (NXZ_LZ77_FUSED_GEN) the finished dynamic-Huffman block with the table of its own counts (`tokens`: nxz_lz77_gen_scratch_bytes())
 	void (*k)(const nxz_batch_job_t *, uint8_t *, uint16_t *, nxz_batch_result_t *, uint32_t *, uint32_t, uint32_t *);
+	// The counts of count == 1 are nxzsc::count_kernel's (nxz_symcount.hip), launched behind the form that does not count: nothing
+	// of the parse needs them, and this kernel has no other work on its CU to hide the counting loops behind.
+	// NXZ_LZ77_COUNT_INKERNEL=1: the form that counts in its out phase instead (read at every call: the tests switch it).
+	const char *cie = getenv("NXZ_LZ77_COUNT_INKERNEL");
+	const bool count_behind = count == 1 && counts && !(cie && atoi(cie) != 0);
+	if (count_behind) count = 0;
 	k = count == 3 ? lz77_kernel<true, false, true> : count == 2 ? lz77_kernel<false, true> : count ? lz77_kernel<true> : lz77_kernel<false>;
 	// per device: the attribute belongs to the loaded code object of a device, and so does the CU count
 	static int ncu_of[64];
@@ -1994,8 +2003,8 @@ static int launch_lz77(int count, const nxz_batch_job_t *jobs, size_t n, uint8_t
 		void (*kd)(const nxz_batch_job_t *, uint8_t *, uint16_t *, nxz_batch_result_t *, uint32_t *, uint32_t, uint32_t *, const uint8_t *);
 		kd = count == 3 ? lz77_dict_kernel<true, false, true> : count == 2 ? lz77_dict_kernel<false, true> : count ? lz77_dict_kernel<true> : lz77_dict_kernel<false>;
 		hipLaunchKernelGGL(kd, dim3(grid), dim3(NT), 0, stream, jobs, tokens, cand2, results, counts, (uint32_t)n, job_counter, dict);
-		return (int)hipGetLastError();
-	}
-	hipLaunchKernelGGL(k, dim3(grid), dim3(NT), 0, stream, jobs, tokens, cand2, results, counts, (uint32_t)n, job_counter);
-	return (int)hipGetLastError();
+	} else
+		hipLaunchKernelGGL(k, dim3(grid), dim3(NT), 0, stream, jobs, tokens, cand2, results, counts, (uint32_t)n, job_counter);
+	const int rc = (int)hipGetLastError();
+	return rc || !count_behind ? rc : nxz_launch_symcount(jobs, n, tokens, counts, stream);
 }

@@ -45,7 +45,7 @@ for k, v in pmc.items():
     rep[k] = o
 json.dump(rep, open(prefix + "_pmc_counters.json", "w"), indent=1, sort_keys=True)
 for name, lz, en, extra in (("fht", "nxzl77::lz77_kernel<false>", "nxze::encode_kernel<false>", []),
-                            ("dhtgen", "nxzl77::lz77_kernel<true>", "nxze::encode_kernel<true>", ["nxzd::dhtgen_kernel"])):
+                            ("dhtgen", "nxzl77::lz77_kernel<true>", "nxze::encode_kernel<true>", ["nxzsc::count_kernel", "nxzd::dhtgen_kernel"])):
     ks = [lz, en] + extra
     t = sum(rep[k]["hbm_read_bytes_per_job_corrected"] + rep[k]["hbm_write_bytes_per_job"] for k in ks if k in rep)
     json.dump({"command": "rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python tools/bench_split.py 65536",

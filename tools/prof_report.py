@@ -61,7 +61,7 @@ for leg in LEGS:
     write, _ = pmc(leg, "write")
     per = {}
     # which kernels belong to the leg's timed work (inflate_own runs one deflate pass to make its input)
-    skip = ("nxzl77::", "nxze::", "nxzd::") if leg.startswith("inflate") else ()
+    skip = ("nxzl77::", "nxzsc::", "nxze::", "nxzd::") if leg.startswith("inflate") else ()
     own_units = {"inflate_own": info["units"] * 2}.get(leg, units)
     for k in sorted(set(fetch) | set(write)):
         if k.startswith(skip):
