@@ -368,17 +368,21 @@ int nxz_batch_wrap(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n,
  * member's own size - 1 (the BGZF layout: readers can find every member without inflating),
  * job i's output -- or, when the job failed or did not shrink (CC != 0 or tpbc >= length + 5), a
  * stored block of its source, the per-job fallback of lib/nx_deflate.c:1292-1400 --, CRC32 and
- * ISIZE.  jobs[].dst must be 16-byte aligned as the compress batch requires; source blocks of
- * at most 65 280 bytes keep every member within BGZF's 64 KiB.  offsets (device, n + 1
+ * ISIZE.  A stored block holds 65 535 bytes at most: a source of 65 536 bytes falls back to two,
+ * 65 535 bytes and the rest, 10 bytes of headers instead of 5.  jobs[].dst must be 16-byte
+ * aligned as the compress batch requires; `packed` may have any alignment.  Source blocks of
+ * at most 65 280 bytes keep every member within BGZF's 64 KiB; a larger member is valid gzip
+ * but NOT a BGZF member -- its BSIZE holds the low 16 bits of size - 1.  offsets (device, n + 1
  * uint64): start of each member in `packed`; offsets[n] = total bytes.  `packed` needs
- * n * 26 + sum(max(tpbc, length + 5)) bytes at most.  Asynchronous on `stream`. */
+ * n * 26 + sum(max(tpbc, length + 5)) bytes at most, length + 10 in place of length + 5 for a
+ * job of more than 65 535 source bytes.  Asynchronous on `stream`. */
 int nxz_batch_pack_gzip(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
 			size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
 
 /* The zlib counterpart (RFC 1950): member i = CMF 0x78 and FLG with FLEVEL from `level` (0..9, -1 = 6, as
  * zlib's deflateInit), job i's output -- or the same stored-block fallback as above --, the Adler-32 of
- * results[i] big-endian.  offsets as above; `packed` needs n * 6 + sum(max(tpbc, length + 5)) bytes at most.
- * Asynchronous on `stream`. */
+ * results[i] big-endian.  offsets as above; `packed` needs n * 6 + sum(max(tpbc, length + 5)) bytes at most
+ * (length + 10 for a job of more than 65 535 source bytes: two stored blocks).  Asynchronous on `stream`. */
 int nxz_batch_pack_zlib(nxz_ctx_t *ctx, int level, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results,
 			size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
 
@@ -481,7 +485,7 @@ int nxz_batch_decompress_dict(nxz_ctx_t *ctx, const nxz_dict_t *dict, const nxz_
 
 /* nxz_batch_pack_zlib for streams made by nxz_batch_compress_dict: FDICT set, FCHECK to match, DICTID (4 bytes, big-endian)
  * behind FLG -- the header zlib's deflate writes after deflateSetDictionary; for an empty dictionary still FDICT, DICTID 1.
- * `packed` needs n * 10 + sum(max(tpbc, length + 5)) bytes at most. */
+ * `packed` needs n * 10 + sum(max(tpbc, length + 5)) bytes at most (length + 10 for a job of more than 65 535 source bytes). */
 int nxz_batch_pack_zlib_dict(nxz_ctx_t *ctx, int level, const nxz_dict_t *dict, const nxz_batch_job_t *jobs,
 			     const nxz_batch_result_t *results, size_t n, uint64_t *offsets, uint8_t *packed, void *stream);
 

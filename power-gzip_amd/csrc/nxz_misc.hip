@@ -239,6 +239,28 @@ __device__ inline bool member_stored(const nxz_batch_job_t &job, const nxz_batch
 	return r.cc != 0 || r.tpbc >= len + 5;
 }
 
+// the stored fallback of `len` source bytes: one stored block, or -- LEN is a 16-bit field -- two for a source of more than
+// 65 535 bytes, 65 535 + the rest with BFINAL on the second only, as stream_piece / pack_block (nxz_pack_block.h) lay them out
+__device__ inline uint32_t stored_size(uint32_t len) { return len + (len > 65535 ? 10 : 5); }
+
+__device__ inline uint32_t member_payload(const nxz_batch_job_t &job, const nxz_batch_result_t &r)
+{
+	return member_stored(job, r) ? stored_size(job.src_len - job.hist_len) : r.tpbc;
+}
+
+// byte k of that fallback: [BFINAL BTYPE=00, LEN, NLEN][first][the same for the rest][rest]
+__device__ inline uint32_t stored_byte(uint32_t k, uint32_t len, const uint8_t *data)
+{
+	const uint32_t first = len > 65535 ? 65535 : len, rest = len - first;
+	auto hdr = [](uint32_t k, uint32_t n, bool last) -> uint32_t {
+		return k == 0 ? (last ? 1u : 0u) : k < 3 ? (n >> (8 * (k - 1))) & 0xff : (~n >> (8 * (k - 3))) & 0xff;
+	};
+	if (k < 5) return hdr(k, first, rest == 0);
+	if (k < 5 + first) return data[k - 5];
+	if (k < 10 + first) return hdr(k - 5 - first, rest, true);
+	return data[k - 10];
+}
+
 // offsets[0..n]: exclusive prefix sum of the member sizes; one workgroup
 __global__ __launch_bounds__(1024) void member_offsets_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
 							      uint32_t n, uint64_t *__restrict__ offsets)
@@ -251,7 +273,7 @@ __global__ __launch_bounds__(1024) void member_offsets_kernel(const nxz_batch_jo
 	for (uint32_t i = lo; i < hi; i++) {
 		const nxz_batch_job_t job = jobs[i];
 		const nxz_batch_result_t r = results[i];
-		sum += NXZ_MEMBER_OVERHEAD + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
+		sum += NXZ_MEMBER_OVERHEAD + member_payload(job, r);
 	}
 	part[t] = sum;
 	__syncthreads();
@@ -266,13 +288,13 @@ __global__ __launch_bounds__(1024) void member_offsets_kernel(const nxz_batch_jo
 		const nxz_batch_job_t job = jobs[i];
 		const nxz_batch_result_t r = results[i];
 		offsets[i] = off;
-		off += NXZ_MEMBER_OVERHEAD + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
+		off += NXZ_MEMBER_OVERHEAD + member_payload(job, r);
 	}
 	if (t == 1023) offsets[n] = part[1023];
 }
 
-// one workgroup per member: header, payload (the job's output, or 5 bytes of stored-block header and
-// the source), trailer.  Whole dwords of the packed buffer are stored at once where the member
+// one workgroup per member: header, payload (the job's output, or the source as stored block(s):
+// stored_byte), trailer.  Whole dwords of the packed buffer are stored at once where the member
 // covers them; the payload bytes of such a dword come from two aligned dword loads.
 __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
 							   const uint64_t *__restrict__ offsets, uint8_t *__restrict__ packed)
@@ -283,10 +305,10 @@ __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t
 	const uint64_t off = offsets[blockIdx.x];
 	const uint32_t len = job.src_len - job.hist_len;
 	const bool stored = member_stored(job, r);
-	const uint32_t paylen = stored ? 5 + len : r.tpbc;
+	const uint32_t paylen = member_payload(job, r);
 	const uint32_t size = NXZ_MEMBER_OVERHEAD + paylen;
 	const uint32_t d0 = stored ? 23 : 18;                         // first member byte that comes from `data`
-	const uint32_t dn = stored ? len : r.tpbc;
+	const uint32_t dn = stored ? (len > 65535 ? 65535 : len) : r.tpbc;   // ... and how many follow it in one piece
 	const uint8_t *data = stored ? job.src + job.hist_len : job.dst;
 	const uint32_t bsize = size - 1;
 	auto byte_at = [&](uint32_t j) -> uint32_t {
@@ -296,12 +318,8 @@ __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t
 			return j < 4 ? (h0 >> (8 * j)) & 0xff : j < 8 ? 0 : j < 12 ? (h2 >> (8 * (j - 8))) & 0xff :
 			       j < 16 ? (h3 >> (8 * (j - 12))) & 0xff : (bsize >> (8 * (j - 16))) & 0xff;
 		}
-		if (j < d0) {                                           // stored block: BFINAL=1 BTYPE=00, LEN, NLEN
-			const uint32_t k = j - 18;
-			return k == 0 ? 1 : k < 3 ? (len >> (8 * (k - 1))) & 0xff : (~len >> (8 * (k - 3))) & 0xff;
-		}
-		if (j < d0 + dn) return data[j - d0];
-		const uint32_t k = j - d0 - dn;                         // CRC32, ISIZE
+		if (j < 18 + paylen) return stored ? stored_byte(j - 18, len, data) : data[j - 18];
+		const uint32_t k = j - 18 - paylen;                     // CRC32, ISIZE
 		return k < 4 ? (r.crc >> (8 * k)) & 0xff : (len >> (8 * (k - 4))) & 0xff;
 	};
 	uint8_t *o = packed + off;
@@ -333,7 +351,7 @@ __global__ __launch_bounds__(256) void pack_members_kernel(const nxz_batch_job_t
 
 __device__ inline uint32_t zlib_member_size(const nxz_batch_job_t &job, const nxz_batch_result_t &r, uint32_t extra = 0)
 {
-	return NXZ_ZLIB_OVERHEAD + extra + (member_stored(job, r) ? 5 + (job.src_len - job.hist_len) : r.tpbc);
+	return NXZ_ZLIB_OVERHEAD + extra + member_payload(job, r);
 }
 
 // (FDICT: the streams name a preset dictionary -- four bytes of DICTID behind FLG, nxz_batch_pack_zlib_dict)
@@ -388,17 +406,14 @@ __device__ __forceinline__ void pack_zlib_body(const nxz_batch_job_t *__restrict
 	const bool stored = member_stored(job, r);
 	const uint32_t size = zlib_member_size(job, r, X);
 	const uint32_t d0 = (stored ? 7 : 2) + X;                     // first byte that comes from `data`
-	const uint32_t dn = stored ? len : r.tpbc;
+	const uint32_t dn = stored ? (len > 65535 ? 65535 : len) : r.tpbc;   // ... and how many follow it in one piece
+	const uint32_t paylen = member_payload(job, r);
 	const uint8_t *data = stored ? job.src + job.hist_len : job.dst;
 	auto byte_at = [&](uint32_t j) -> uint32_t {
 		if (j < 2) return j == 0 ? 0x78u : flg;                 // CM 8, CINFO 7 (a 32 KiB window)
 		if (FDICT && j < 6) return (dictid >> (8 * (5 - j))) & 0xff;   // DICTID, most significant byte first
-		if (j < d0) {                                           // stored block: BFINAL=1 BTYPE=00, LEN, NLEN
-			const uint32_t k = j - 2 - X;
-			return k == 0 ? 1 : k < 3 ? (len >> (8 * (k - 1))) & 0xff : (~len >> (8 * (k - 3))) & 0xff;
-		}
-		if (j < d0 + dn) return data[j - d0];
-		return (r.adler >> (8 * (3 - (j - d0 - dn)))) & 0xff;   // Adler-32, most significant byte first
+		if (j < 2 + X + paylen) return stored ? stored_byte(j - 2 - X, len, data) : data[j - 2 - X];
+		return (r.adler >> (8 * (3 - (j - 2 - X - paylen)))) & 0xff;   // Adler-32, most significant byte first
 	};
 	uint8_t *o = packed + off;
 	const uint32_t head = (uint32_t)((4 - ((uintptr_t)o & 3)) & 3);
