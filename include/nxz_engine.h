@@ -739,7 +739,8 @@ enum {
 	NXZ_RANGE_OK = 0,
 	NXZ_RANGE_OUT_OF_BOUNDS, /* begin > end, begin < uoff[0] or end > uoff[L] (after conversion): no bytes */
 	NXZ_RANGE_BAD_VOFFSET,   /* voff >> 16 is no coff[j], or voff & 0xffff exceeds that member's ISIZE: no bytes */
-	NXZ_RANGE_DAMAGED        /* a member it touches failed its framed decode, or its ISIZE is not uoff[j+1] - uoff[j]: zeros */
+	NXZ_RANGE_DAMAGED,       /* a member it touches failed its framed decode, or its ISIZE is not uoff[j+1] - uoff[j]: zeros */
+	NXZ_RANGE_BAD_STREAM = 4 /* nxz_batch_checkpoint_read_ranges only: the range's job has no index row to read through: no bytes */
 };
 
 /* Reads n ranges of a BGZF image.  coff / uoff (DEVICE, nidx = members + 1 entries) is an index as nxz_bgzf_index
@@ -922,6 +923,60 @@ int nxz_checkpoint_read_ranges_fine(nxz_ctx_t *ctx, const uint8_t *src, uint64_t
 				    uint64_t nidx /* count + 1 */, const nxz_bgzf_range_t *ranges, size_t n,
 				    uint8_t *dst, uint64_t dst_cap, uint64_t *offsets, uint32_t *status,   /* NXZ_RANGE_* */
 				    uint64_t *out_len, uint64_t *decoded, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Batched range reads: ranges across all the streams of an indexed batch, in one call
+ * ---------------------------------------------------------------------- */
+/* The three index calls take n jobs and write n rows; the two readers above take ONE row and wait for the host twice a call.  This
+ * call takes the batch's index as the index calls wrote it -- thousands of resident shards, a few records wanted from each -- and
+ * reads ranges of any of its streams: one map, one decode batch over the segments of all streams, the same two waits for the whole
+ * batch (power-gzip_amd/csrc/nxz_checkpoint_batch.hip; the rules in nxz_checkpoint_batch.h).
+ * jobs (DEVICE, n_jobs) is the array the index call was given: src and src_len are read, dst is not.  cbit / uoff (DEVICE,
+ * n_jobs * (cp_cap + 1)), state (the same, or NULL: a coarse index), windows (DEVICE, n_jobs * cp_cap slots of 32768 bytes) and
+ * streams (DEVICE, n_jobs) are what nxz_batch_checkpoint_index / _index_fine / _build wrote, with the same cp_cap.
+ * Per range: ranges[r] = (job, begin, end) reads [begin, end) of the uncompressed bytes of stream `job` exactly as
+ * nxz_checkpoint_read_ranges (state == NULL) / nxz_checkpoint_read_ranges_fine (state) reads it through row `job`: the same
+ * upper-bound rule onto segments; an empty range is NXZ_RANGE_OK with no bytes; begin > end or end > out_len (the row's sentinel
+ * uoff) is NXZ_RANGE_OUT_OF_BOUNDS; a range that touches a segment that is not good is NXZ_RANGE_DAMAGED and reads as zeros.
+ * offsets (DEVICE, n + 1) is the exclusive prefix sum of the OK ranges' lengths in the order of `ranges`; ranges may name jobs in any
+ * order, and any number of them the same job.  Every segment of every stream is decoded at most once per call, however many ranges
+ * touch it; *decoded = the distinct segments inflated over the whole batch.
+ * A stream's validity is that stream's alone: a range is NXZ_RANGE_BAD_STREAM (no bytes, length 0 in offsets) when job >= n_jobs,
+ * streams[job].status != NXZ_CPS_OK, streams[job].count is 0 or exceeds cp_cap, jobs[job].src is NULL, the row fails rule 5 against
+ * jobs[job].src_len or, with state, a per-entry check listed at nxz_checkpoint_read_ranges_fine.  Ranges of other streams are
+ * unaffected, and this call never returns -EILSEQ: one stale row does not cost a caller the others.  The single-stream calls'
+ * guarantee holds row by row: a stale or foreign row never makes a kernel read outside that job's src, its own cp_cap window slots
+ * or a table slot.  (Every row is checked, named by a range or not: a thread an entry.)
+ * state == NULL reads exactly what a state array of zeros reads.  With state a segment's job is the fine reader's: resume =
+ * state.resume | in_subc << 20, NXZ_JOB_SUSPEND_WHEN_FULL, a target of exactly the segment's output and, inside a dynamic block, the
+ * table -- bits [tbit, tbit + dhtlen) of that job's src -- in a nxz_batch_dht_t slot.  Segments are staged as [window][source bytes]
+ * and go through nxz_batch_decompress as one batch over all streams, in chunks of at most NXZ_BGZF_CHUNK segments and 1 GiB; a chunk
+ * may hold segments of many streams.
+ * Synchronous: the two waits of the single-stream call, once.  Returns 0 (n == 0 or n_jobs == 0 included: *out_len = 0, and with
+ * n_jobs == 0 every range is NXZ_RANGE_BAD_STREAM); -E2BIG, *out_len and dst == NULL sizing exactly as there (offsets and status
+ * written, dst not); -EINVAL: ctx, cbit, uoff, windows, streams or offsets NULL, jobs NULL with n_jobs > 0, cp_cap == 0,
+ * n_jobs >= 2^31, n >= 2^31, n_jobs * (cp_cap + 1) >= 2^32, ranges or status NULL with n > 0; -ENODEV in a forked child; -ENOMEM
+ * when scratch cannot be had.
+ * Not part of this call: BGZF images (nxz_bgzf_read_ranges stays single-image); multi-member gzip jobs (the first member is what the
+ * index holds); an asynchronous form.
+ * Speed (profiles/r22_checkpoint_batch.txt, MI355X; tools/bench_checkpoint_batch.py), against the loop of nxz_checkpoint_read_ranges_fine
+ * calls over the same ranges, one 4 KiB range a stream: 0.017 of the loop's time on 64 zlib -6 streams of 16 MiB (4.1 ms against 240 ms
+ * at a span of 64 KiB, 61 ms against 3.7 s at 1 MiB) and 0.001 - 0.004 on 4096 streams of 1 MiB (7.9 ms against 15.4 s, 41 ms against
+ * 10.5 s); the whole stream as the range, 4096 x 1 MiB: 0.004 - 0.006 (95 ms against 16.6 s, 42 ms against 10.5 s: 42 and 95 GiB/s of
+ * output).  The batched call is slower at none of these points. */
+typedef struct nxz_batch_range {     /* DEVICE, 24 bytes */
+	uint32_t job;                /* row of the index: 0 .. n_jobs - 1 */
+	uint32_t reserved;           /* 0 */
+	uint64_t begin, end;         /* uncompressed offsets of that stream, [begin, end) */
+} nxz_batch_range_t;
+int nxz_batch_checkpoint_read_ranges(nxz_ctx_t *ctx, const nxz_batch_job_t *jobs, size_t n_jobs, uint32_t cp_cap,
+				     const uint64_t *cbit, const uint64_t *uoff,          /* DEVICE, n_jobs * (cp_cap + 1) each */
+				     const nxz_checkpoint_state_t *state,                 /* DEVICE, n_jobs * (cp_cap + 1), or NULL: a coarse index */
+				     const uint8_t *windows,                              /* DEVICE, n_jobs * cp_cap * 32768 */
+				     const nxz_checkpoint_stream_t *streams,              /* DEVICE, n_jobs */
+				     const nxz_batch_range_t *ranges, size_t n,           /* DEVICE */
+				     uint8_t *dst, uint64_t dst_cap, uint64_t *offsets /* n + 1 */, uint32_t *status /* n, NXZ_RANGE_* */,
+				     uint64_t *out_len, uint64_t *decoded, void *stream);
 
 /* Device memory, pinned host memory, streams and asynchronous copies, for callers that hold
  * host buffers and do not link the HIP runtime themselves.  A stream made here is passed as

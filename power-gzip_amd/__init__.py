@@ -14,4 +14,4 @@ from .engine import (Engine, EngineError, JOB_DTYPE, RESULT_DTYPE, DHT_DTYPE, li
                      RANGE_BAD_VOFFSET, RANGE_DAMAGED, Dict, JOB_SUSPEND_WHEN_FULL, JOB_NO_DICT, dict_inflate_window,
                      dict_deflate_window, stream_dict_window, GZIP_MEMBER_DTYPE, GZIP_STREAM_DTYPE, GZS_OK, GZS_MEMBER_FAILED, GZS_MORE_MEMBERS,
                      GZS_TARGET_SPACE, GZS_INVALID, CHECKPOINT_STREAM_DTYPE, CHECKPOINT_WINDOW, CHECKPOINT_STATE_DTYPE, CHECKPOINT_SPAN_MIN, CPS_OK, CPS_STREAM_FAILED, CPS_MORE,
-                     CPS_NO_OUTPUT, CPS_INVALID)
+                     CPS_NO_OUTPUT, CPS_INVALID, RANGE_BAD_STREAM, BATCH_RANGE_DTYPE)

@@ -1,10 +1,11 @@
 // nxz_batch_framed.cpp -- the calls of include/nxz_engine.h's device-resident interface that put kernels of their own around a raw
 // batch (nxz_batch.cpp) or walk streams without decoding them: framed zlib / gzip streams, output sizes, multi-member gzip jobs,
-// one stream per device buffer, BGZF discovery, index and range reads, checkpoint index and range reads.
+// one stream per device buffer, BGZF discovery, index and range reads, checkpoint index and range reads (one stream's, and a batch's).
 #include <functional>
 #include "nxz_ctx.h"
 #include "nxz_streams_dict.h"
 #include "nxz_checkpoint_fine.h"
+#include "nxz_checkpoint_batch.h"
 
 // ---------------------------------------------------------------------------
 // Framed streams (nxz_frame.hip): header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`.
@@ -679,4 +680,55 @@ extern "C" int nxz_checkpoint_read_ranges_fine(nxz_ctx_t *c, const uint8_t *src,
 	steps.dht_slots = true;
 	steps.gather_what = "fine checkpoint gather launch"; steps.zero_what = "fine checkpoint zero launch";
 	return read_ranges_locked(c, s, steps, uoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
+}
+
+// ---------------------------------------------------------------------------
+// Ranges across all the rows of a batch's index (nxz_checkpoint_batch.hip, the rules in nxz_checkpoint_batch.h): the same driver once
+// more.  The batch is ONE index of n_jobs * (cp_cap + 1) entries with a uoff of its own in BUF_RNG_BATCH; a row that is not good
+// costs its ranges their bytes (NXZ_RANGE_BAD_STREAM), never the call (ctl[0] stays 0: no -EILSEQ).  With state a chunk is the fine
+// reader's, else the coarse reader's; its segments come from any of the streams.
+// ---------------------------------------------------------------------------
+extern "C" int nxz_batch_checkpoint_read_ranges(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n_jobs, uint32_t cp_cap, const uint64_t *cbit,
+						const uint64_t *uoff, const nxz_checkpoint_state_t *state, const uint8_t *windows,
+						const nxz_checkpoint_stream_t *streams, const nxz_batch_range_t *ranges, size_t n, uint8_t *dst,
+						uint64_t dst_cap, uint64_t *offsets, uint32_t *status, uint64_t *out_len, uint64_t *decoded, void *stream)
+{
+	if (out_len) *out_len = 0;
+	if (decoded) *decoded = 0;
+	if (!c || !cbit || !uoff || !windows || !streams || !offsets || (n_jobs && !jobs) || (n && (!ranges || !status)) || n >= (1ull << 31) ||
+	    !nxz_cpb_shape_ok(n_jobs, cp_cap))
+		return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	if (!n || !n_jobs) {                                                  // no range, or no row for any range to name
+		HIPCHK(hipMemsetAsync(offsets, 0, (n + 1) * sizeof(uint64_t), s), return -EIO);
+		if (n) HIPCHK(hipMemsetD32Async((hipDeviceptr_t)status, NXZ_RANGE_BAD_STREAM, n, s), return -EIO);
+		HIPCHK(hipStreamSynchronize(s), return -EIO);
+		return 0;
+	}
+	const uint64_t L = nxz_cpb_entries(n_jobs, cp_cap) - 1;
+	uint8_t *const bws = with_scratch(c, s, [&](nxz_ctx::Scratch &sc) {
+		(void)sc.buf[BUF_RNG_BATCH].grow(s, nxz_checkpoint_batch_workspace(n_jobs, cp_cap, n));
+		return sc.buf[BUF_RNG_BATCH].p;
+	});
+	if (!bws) return -ENOMEM;
+	const uint64_t *const fuoff = nxz_checkpoint_batch_uoff(bws, n_jobs, cp_cap, n);
+	RangeSteps steps;
+	steps.map = [&](uint8_t *ws) {
+		return launched("checkpoint batch map launch", nxz_launch_checkpoint_batch_map(jobs, n_jobs, cp_cap, cbit, uoff, state, streams, ranges, n, offsets,
+											       status, bws, ws, s));
+	};
+	steps.chunk = [&](uint8_t *ws, uint64_t k0, uint64_t cnt, const RangeSlots &sl) {
+		int rc = launched("checkpoint batch stage launch", nxz_launch_checkpoint_batch_stage(jobs, n_jobs, cp_cap, cbit, uoff, state, windows, streams, n, bws, ws,
+												     k0, cnt, sl.islots, sl.istride, sl.oslots, sl.ostride, sl.jobs,
+												     sl.dht, s));
+		if (!rc) rc = batch_decompress(c, sl.jobs, (size_t)cnt, sl.results, state ? sl.dht : nullptr, s, state ? fine_chunk_route() : 0);
+		return rc ? rc : launched("checkpoint batch verdict launch", nxz_launch_checkpoint_verdict(fuoff, n, L, ws, k0, cnt, sl.results, sl.frames, s));
+	};
+	steps.input_slots = true;
+	steps.dht_slots = state != nullptr;
+	steps.gather_what = "checkpoint batch gather launch"; steps.zero_what = "checkpoint batch zero launch";
+	return read_ranges_locked(c, s, steps, fuoff, L, n, dst, dst_cap, offsets, status, out_len, decoded);
 }

@@ -198,6 +198,20 @@ int nxz_launch_checkpoint_jobs_fine(const uint8_t *src, const uint64_t *cbit, co
 int nxz_launch_checkpoint_build(int fmt, const nxz_batch_job_t *jobs, size_t n, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
 				nxz_checkpoint_state_t *state, uint8_t *windows, nxz_checkpoint_stream_t *streams, const uint32_t *order,
 				hipStream_t stream);
+/* nxz_checkpoint_batch.hip: ranges over all the rows of a batch's index (nxz_checkpoint_batch.h has the rules).  The batch is ONE
+ * index of n_jobs * (cp_cap + 1) entries with a uoff of its own in bws (nxz_checkpoint_batch_workspace bytes; _uoff: where), which
+ * the map, gather, inmax and verdict launches above take as it is.  map: the rows' verdicts, the bases, the flat uoff, the ranges
+ * onto it, nxz_launch_range_map_ranges, the statuses of ranges without a row, nxz_launch_checkpoint_inmax; stage:
+ * nxz_launch_checkpoint_stage and, with state, nxz_launch_checkpoint_jobs_fine, the source and the window by the segment's row */
+size_t nxz_checkpoint_batch_workspace(uint64_t n_jobs, uint32_t cp_cap, uint64_t n);
+const uint64_t *nxz_checkpoint_batch_uoff(uint8_t *bws, uint64_t n_jobs, uint32_t cp_cap, uint64_t n);
+int nxz_launch_checkpoint_batch_map(const nxz_batch_job_t *jobs, uint64_t n_jobs, uint32_t cp_cap, const uint64_t *cbit, const uint64_t *uoff,
+				    const nxz_checkpoint_state_t *state, const nxz_checkpoint_stream_t *streams, const nxz_batch_range_t *ranges,
+				    uint64_t n, uint64_t *offsets, uint32_t *status, uint8_t *bws, uint8_t *ws, hipStream_t stream);
+int nxz_launch_checkpoint_batch_stage(const nxz_batch_job_t *in, uint64_t n_jobs, uint32_t cp_cap, const uint64_t *cbit, const uint64_t *uoff,
+				      const nxz_checkpoint_state_t *state, const uint8_t *windows, const nxz_checkpoint_stream_t *streams,
+				      uint64_t n, uint8_t *bws, uint8_t *ws, uint64_t k0, uint64_t cnt, uint8_t *islots, uint64_t istride,
+				      uint8_t *oslots, uint64_t ostride, nxz_batch_job_t *jobs, nxz_batch_dht_t *dht, hipStream_t stream);
 /* nxz_streams.hip: a stream per device buffer (nxz_batch_deflate_streams; nxz_streams.h has the rules).  desc: the caller's jobs;
  * first[n + 1]: the streams' block prefix; a chunk is the blocks [b0, b0 + m) of the batch: jobs, results, owner (the block's stream)
  * and offsets (where it goes in its stream) are indexed from b0; state: what a stream carries from chunk to chunk */

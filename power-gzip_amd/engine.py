@@ -59,7 +59,7 @@ GZS_OK, GZS_MEMBER_FAILED, GZS_MORE_MEMBERS, GZS_TARGET_SPACE, GZS_INVALID = ran
 
 # BGZF random access (include/nxz_engine.h: nxz_bgzf_index / nxz_bgzf_read_ranges)
 RANGE_UOFF, RANGE_VOFF = 0, 1
-RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED = range(4)
+RANGE_OK, RANGE_OUT_OF_BOUNDS, RANGE_BAD_VOFFSET, RANGE_DAMAGED, RANGE_BAD_STREAM = range(5)
 
 # checkpoints inside raw / zlib / gzip streams (include/nxz_engine.h: nxz_batch_checkpoint_index / nxz_checkpoint_read_ranges)
 CHECKPOINT_STREAM_DTYPE = np.dtype([("status", "<u4"), ("count", "<u4"), ("format", "<u4"), ("hdr_len", "<u4"), ("out_len", "<u8"),
@@ -71,6 +71,9 @@ CHECKPOINT_WINDOW = 32768
 CHECKPOINT_STATE_DTYPE = np.dtype([("tbit", "<u8"), ("resume", "<u4"), ("dhtlen", "<u4")])
 assert CHECKPOINT_STATE_DTYPE.itemsize == 16
 CHECKPOINT_SPAN_MIN = 258
+# ... and ranges across all the rows of a batch's index (nxz_batch_checkpoint_read_ranges): job, then [begin, end) of that stream
+BATCH_RANGE_DTYPE = np.dtype([("job", "<u4"), ("reserved", "<u4"), ("begin", "<u8"), ("end", "<u8")])
+assert BATCH_RANGE_DTYPE.itemsize == 24
 
 
 # jobs[].reserved (include/nxz_engine.h)
@@ -205,6 +208,9 @@ def load_library():
         L.nxz_checkpoint_read_ranges_fine.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
                                                       C.POINTER(C.c_uint64), C.c_void_p]
+        L.nxz_batch_checkpoint_read_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_inflate_stream.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
@@ -672,6 +678,36 @@ class Engine:
                                                           windows.data_ptr() if windows is not None else None, cbit.numel(), ranges.data_ptr(), n,
                                                           d.data_ptr() if d is not None else None, cap, offsets.data_ptr(), status.data_ptr(),
                                                           C.byref(out_len), C.byref(decoded), self.stream_handle())
+        if dst is None:                  # (a first call for the size; the second call runs the map again)
+            rc = call(None, 0)
+            dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
+            if rc != -errno.E2BIG:
+                return rc, offsets, status[:n], out_len.value, decoded.value, dst
+        rc = call(dst, dst.numel())
+        return rc, offsets, status[:n], out_len.value, decoded.value, dst
+
+    def checkpoint_read_ranges_batch(self, jobs, n_jobs, cp_cap, cbit, uoff, state, windows, streams, ranges, dst=None, n=None):
+        """nxz_batch_checkpoint_read_ranges: ranges across ALL the streams of an indexed batch in one call.  jobs: the device tensor
+        of n_jobs JOB_DTYPE records the index call was given; cbit / uoff / state / windows / streams: what checkpoint_index,
+        checkpoint_index_fine or checkpoint_build returned for them with the same cp_cap (state None: a coarse index); ranges: a
+        contiguous uint8 device tensor of BATCH_RANGE_DTYPE records (n of them: all by default).  Any tensor may be None (the call
+        then says -EINVAL).  Returns (rc, offsets, status, out_len, decoded, dst) as checkpoint_read_ranges does."""
+        t = self.torch
+        if n is None:
+            n = ranges.numel() // BATCH_RANGE_DTYPE.itemsize
+        offsets = t.zeros(n + 1, dtype=t.int64, device=self.dev)
+        status = t.zeros(max(n, 1), dtype=t.int32, device=self.dev)
+        out_len, decoded = C.c_uint64(), C.c_uint64()
+        for x in (jobs, cbit, uoff, state, windows, streams, ranges):
+            assert x is None or x.is_contiguous()
+
+        def ptr(x):
+            return x.data_ptr() if x is not None else None
+
+        def call(d, cap):
+            return self.L.nxz_batch_checkpoint_read_ranges(self.ctx, ptr(jobs), n_jobs, cp_cap, ptr(cbit), ptr(uoff), ptr(state), ptr(windows),
+                                                           ptr(streams), ptr(ranges), n, ptr(d), cap, offsets.data_ptr(), status.data_ptr(),
+                                                           C.byref(out_len), C.byref(decoded), self.stream_handle())
         if dst is None:                  # (a first call for the size; the second call runs the map again)
             rc = call(None, 0)
             dst = t.empty(max(out_len.value, 1), dtype=t.uint8, device=self.dev)
