@@ -688,6 +688,49 @@ int nxz_batch_deflate_streams(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32
 			      const nxz_stream_job_t *jobs /* HOST */, size_t n,
 			      nxz_stream_result_t *results /* DEVICE */, void *stream);
 
+/* The same call with the streams' CHECKPOINT INDEX as a by-product (the checkpoint section below has the index's rules, its
+ * arrays and its readers): the call laid every block into its stream at a known byte, so it writes the rows that
+ * nxz_batch_checkpoint_index would find by walking the finished streams -- without decoding anything and without the host wait
+ * for out_len that building the index jobs costs.  Everything up to `results` is nxz_batch_deflate_streams's: the bytes at every
+ * dst and every results[i] are exactly what that call writes for the same arguments.
+ * Row i -- cbit / uoff [i * (cp_cap + 1) + k], streams[i] and, with windows, slots i * cp_cap + k -- is exactly what
+ * nxz_batch_checkpoint_index(fmt, job{src = jobs[i].dst, src_len = out_len, dst = jobs[i].src, dst_cap = src_len}, span, cp_cap, ...)
+ * writes: rules 1 to 5, the sentinel at [count] when count <= cp_cap, NXZ_CPS_MORE with the true count and no sentinel beyond that,
+ * format = fmt, hdr_len, out_len = src_len.  A checkpoint may stand inside a byte (the empty stored block behind a block that ends
+ * inside one).  windows (DEVICE, n * cp_cap slots of 32768 bytes, or NULL: positions only): the first min(uoff[k], 32768) bytes of
+ * slot i * cp_cap + k are jobs[i].src[uoff[k] - w, uoff[k]); the rest of a slot and the slots beyond the stored checkpoints are not
+ * written.
+ * A stream that gets no index: one the compress side refuses (results[i].cc != 0), or one whose src_len or out_len does not fit 32
+ * bits -- the limit of the index format; it is compressed all the same.  streams[i].status = NXZ_CPS_INVALID, count = 0,
+ * cc = results[i].cc; its row and slots are not written (of a stream whose src_len fits and whose out_len turns out not to, the
+ * entries found before the end are), the neighbours are unaffected.
+ * index_jobs (DEVICE, n, or NULL): index_jobs[i] = the job the readers want -- src = jobs[i].dst, src_len = out_len, dst = NULL,
+ * in_adler = 1, every other field 0; src = NULL and src_len = 0 for a stream without an index.  Then
+ * nxz_batch_checkpoint_read_ranges(ctx, index_jobs, n, cp_cap, cbit, uoff, NULL, windows, streams, ...) reads ranges with no host
+ * step in between.
+ * On the device (power-gzip_amd/csrc/nxz_streams_index.hip, the rules in nxz_streams_index.h): per chunk a sweep over the block headers
+ * behind the layout -- a wavefront a stream, one step per checkpoint found; (c, count) go from chunk to chunk, the index does not
+ * depend on NXZ_STREAMS_CHUNK -- and a copy of the windows beside the packing, 32 KiB per stored checkpoint: at span = B half the
+ * source again.  Asynchronous on `stream`: no host wait and no allocation once the stream's scratch has grown.
+ * Returns as nxz_batch_deflate_streams, and -EINVAL for span == 0, cp_cap == 0, cbit, uoff or streams NULL with n > 0,
+ * n * (cp_cap + 1) >= 2^32.
+ * Not part of this call: the dictionary form (a first segment whose window is the dictionary has no place in the row format);
+ * checkpoints inside blocks (a reader passes state == NULL); compressing or deduplicating the windows.
+ * Speed (tools/bench_streams_indexed.py, profiles/r23_streams_indexed.txt; zlib, DHTGEN, hist_max 0 and 32768, a checkpoint every 64 KiB
+ * and every 1 MiB): 1.01 to 1.03 of the time of nxz_batch_deflate_streams alone for 4096 streams of 1 MiB (42.9 against 41.8 ms at
+ * 64 KiB, hist_max 0), 1.04 to 1.07 for 64 streams of 16 MiB (11.4 against 10.7 ms); against the route it replaces -- that call, the
+ * host wait for out_len, jobs built on the host, nxz_batch_checkpoint_index with windows from the source -- 0.34 to 0.40 of the time
+ * for the first shape (124 ms) and 0.015 to 0.02 for the second (753 ms: a wavefront walks 16 MiB). */
+struct nxz_checkpoint_stream;         /* nxz_checkpoint_stream_t, below */
+int nxz_batch_deflate_streams_indexed(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32_t hist_max,
+				      const nxz_stream_job_t *jobs /* HOST */, size_t n, nxz_stream_result_t *results /* DEVICE */,
+				      uint64_t span, uint32_t cp_cap,
+				      uint64_t *cbit, uint64_t *uoff,            /* DEVICE, n * (cp_cap + 1) each */
+				      uint8_t *windows,                          /* DEVICE, n * cp_cap * 32768, or NULL */
+				      struct nxz_checkpoint_stream *streams,     /* DEVICE, n */
+				      nxz_batch_job_t *index_jobs,               /* DEVICE, n, or NULL */
+				      void *stream);
+
 /* The same with ONE preset dictionary for all streams (the device-side deflateSetDictionary for buffers of any length; what
  * nxz_batch_compress_dict + nxz_batch_pack_zlib_dict do for sources that fit one block).  Everything not named here is as in
  * nxz_batch_deflate_streams: jobs, results, fc, level, the chunks, asynchrony.

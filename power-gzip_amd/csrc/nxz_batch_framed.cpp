@@ -4,6 +4,7 @@
 #include <functional>
 #include "nxz_ctx.h"
 #include "nxz_streams_dict.h"
+#include "nxz_streams_index.h"
 #include "nxz_checkpoint_fine.h"
 #include "nxz_checkpoint_batch.h"
 
@@ -220,9 +221,19 @@ extern "C" size_t nxz_deflate_stream_bound_dict(uint64_t src_len, uint32_t hist_
 	return nxz_streams_dict_fmt_ok(fmt) ? (size_t)nxz_streams_dict_bound(src_len, hist_max, fmt) : 0;
 }
 
-// dict: NULL, or the dictionary form (its device checked by the caller)
+// what nxz_batch_deflate_streams_indexed adds to a call: the caller's arrays (its arguments, checked there)
+struct StreamsIndex {
+	uint64_t span;
+	uint32_t cp_cap;
+	uint64_t *cbit, *uoff;
+	uint8_t *windows;
+	nxz_checkpoint_stream_t *streams;
+	nxz_batch_job_t *index_jobs;
+};
+
+// dict: NULL, or the dictionary form (its device checked by the caller); ix: NULL, or the index to write on the way (never with dict)
 static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_dict *dict, const nxz_stream_job_t *jobs, size_t n,
-			   nxz_stream_result_t *results, void *stream)
+			   nxz_stream_result_t *results, void *stream, const StreamsIndex *ix = nullptr)
 {
 	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !(dict ? nxz_streams_dict_fmt_ok(fmt) : nxz_streams_fmt_ok(fmt)) ||
 	    level < -1 || level > 9 || (n && (!jobs || !results))) return -EINVAL;
@@ -276,7 +287,10 @@ static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hi
 		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
 		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), o_ljobs = o_slots + up((size_t)C * NXZ_STREAMS_SLOT),
 		     o_lres = o_ljobs + up((size_t)C * sizeof(nxz_batch_job_t)), o_pos = o_lres + up((size_t)C * sizeof(nxz_batch_result_t)),
-		     d_bytes = split ? o_pos + (size_t)C * sizeof(uint32_t) : o_slots + (size_t)C * NXZ_STREAMS_SLOT;
+		     d_plain = split ? o_pos + (size_t)C * sizeof(uint32_t) : o_slots + (size_t)C * NXZ_STREAMS_SLOT,
+		     // the index's own, behind everything the plain call lays out: a state a stream, two slot marks a block of a chunk
+		     o_ist = up(d_plain), o_marks = o_ist + up(n * sizeof(nxz_stream_index_state_t)),
+		     d_bytes = !ix ? d_plain : ix->windows ? o_marks + (size_t)C * 2 * sizeof(uint32_t) : o_marks;
 	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
 		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
 		return r.buf[BUF_STREAMS].p;
@@ -294,12 +308,16 @@ static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hi
 	nxz_batch_job_t *const d_ljobs = split ? (nxz_batch_job_t *)(d + o_ljobs) : nullptr;
 	nxz_batch_result_t *const d_lres = split ? (nxz_batch_result_t *)(d + o_lres) : nullptr;
 	uint32_t *const d_pos = split ? (uint32_t *)(d + o_pos) : nullptr;
+	nxz_stream_index_state_t *const d_ist = ix ? (nxz_stream_index_state_t *)(d + o_ist) : nullptr;
+	uint32_t *const d_marks = ix && ix->windows ? (uint32_t *)(d + o_marks) : nullptr;
 	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
 	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
 	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
 	int rc = launched("streams prologue launch", dict ? nxz_launch_streams_dict_prologue(d_desc, ns, hist_max, fmt, level, dict->id, d_state, s)
 							  : nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s));
 	if (rc) return rc;
+	if (ix && (rc = launched("streams index prologue launch", nxz_launch_streams_index_prologue(d_desc, ns, fmt, d_state, ix->cp_cap, ix->cbit, ix->uoff,
+												     d_ist, s))) != 0) return rc;
 	const uint32_t op_block = nxz_crc_shift_op(B);
 	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
 	for (uint32_t b0 = 0; b0 < nblk; b0 += C) {
@@ -321,18 +339,37 @@ static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hi
 			if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
 		}
 		rc = nxz_launch_streams_layout(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
+		if (!rc && ix) rc = nxz_launch_streams_index_sweep(d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, d_off, hist_max, ix->span, ix->cp_cap,
+								    ix->cbit, ix->uoff, d_ist, d_marks, s);
 		if (!rc) rc = nxz_launch_streams_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, s);
+		if (!rc && d_marks) rc = nxz_launch_streams_index_windows(d_desc, d_owner, m, d_marks, ix->cp_cap, ix->uoff, ix->windows, s);
 		if ((rc = launched("streams pack launch", rc)) != 0) return rc;
 		i_lo = i_hi;
 	}
-	return launched("streams epilogue launch", dict ? nxz_launch_streams_dict_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s)
-							: nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s));
+	rc = launched("streams epilogue launch", dict ? nxz_launch_streams_dict_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s)
+						      : nxz_launch_streams_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, results, s));
+	if (rc || !ix) return rc;
+	return launched("streams index epilogue launch", nxz_launch_streams_index_epilogue(d_desc, ns, fmt, results, d_ist, ix->cp_cap, ix->cbit, ix->uoff,
+											   ix->streams, ix->index_jobs, s));
 }
 
 extern "C" int nxz_batch_deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
 					 nxz_stream_result_t *results, void *stream)
 {
 	return deflate_streams(c, fc, fmt, level, hist_max, nullptr, jobs, n, results, stream);
+}
+
+// The same call with the streams' checkpoint index as a by-product (nxz_streams_index.hip, the rules in nxz_streams_index.h): behind
+// the prologue checkpoint 0 and the index's per-stream state, per chunk a sweep over the block headers behind layout and the windows'
+// copy beside pack, behind the epilogue the sentinels and the streams' records.  The state and a chunk's slot marks lie behind the
+// plain call's part of BUF_STREAMS; still everything on `s`, and no host wait.
+extern "C" int nxz_batch_deflate_streams_indexed(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_job_t *jobs, size_t n,
+						 nxz_stream_result_t *results, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+						 uint8_t *windows, nxz_checkpoint_stream_t *streams, nxz_batch_job_t *index_jobs, void *stream)
+{
+	if (span == 0 || cp_cap == 0 || (n && (!cbit || !uoff || !streams)) || !nxz_si_shape_ok(n, cp_cap)) return -EINVAL;
+	const StreamsIndex ix = {span, cp_cap, cbit, uoff, windows, streams, index_jobs};
+	return deflate_streams(c, fc, fmt, level, hist_max, nullptr, jobs, n, results, stream, &ix);
 }
 
 extern "C" int nxz_batch_deflate_streams_dict(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_dict_t *dict,

@@ -240,6 +240,22 @@ int nxz_launch_streams_dict_gather(const nxz_batch_result_t *lresults, const uin
 				   hipStream_t stream);
 int nxz_launch_streams_dict_epilogue(const nxz_stream_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
 				     const nxz_stream_state_t *state, nxz_stream_result_t *results, hipStream_t stream);
+/* nxz_streams_index.hip: the checkpoint index of the streams as a by-product of their layout (nxz_batch_deflate_streams_indexed;
+ * nxz_streams_index.h has the rules).  Each launch goes behind its namesake above; ist: the index's own per-stream state (c: the uoff
+ * of the last checkpoint, count: checkpoints so far, end_bit: the sentinel's bit, on: 0 for a stream that gets no index); marks: two
+ * words a block of the chunk -- the window slot of each of its headers, or NXZ_SI_NONE (NULL: no windows wanted) */
+typedef struct nxz_stream_index_state { uint64_t c, end_bit; uint32_t count, on; } nxz_stream_index_state_t;
+int nxz_launch_streams_index_prologue(const nxz_stream_job_t *desc, uint32_t n, int fmt, const nxz_stream_state_t *state, uint32_t cp_cap,
+				      uint64_t *cbit, uint64_t *uoff, nxz_stream_index_state_t *ist, hipStream_t stream);
+int nxz_launch_streams_index_sweep(const uint32_t *first, uint32_t i_lo, uint32_t streams, uint32_t b0, uint32_t m,
+				   const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, const uint64_t *offsets,
+				   uint32_t hist_max, uint64_t span, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+				   nxz_stream_index_state_t *ist, uint32_t *marks, hipStream_t stream);
+int nxz_launch_streams_index_windows(const nxz_stream_job_t *desc, const uint32_t *owner, uint32_t m, const uint32_t *marks,
+				     uint32_t cp_cap, const uint64_t *uoff, uint8_t *windows, hipStream_t stream);
+int nxz_launch_streams_index_epilogue(const nxz_stream_job_t *desc, uint32_t n, int fmt, const nxz_stream_result_t *results,
+				      const nxz_stream_index_state_t *ist, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
+				      nxz_checkpoint_stream_t *streams, nxz_batch_job_t *index_jobs, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

@@ -187,6 +187,9 @@ def load_library():
         L.nxz_batch_deflate_streams.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_void_p]
         L.nxz_deflate_stream_bound_dict.restype = C.c_size_t
+        L.nxz_batch_deflate_streams_indexed.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                        C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]
         L.nxz_deflate_stream_bound_dict.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
         L.nxz_batch_deflate_streams_dict.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                                      C.c_void_p, C.c_void_p]
@@ -472,6 +475,51 @@ class Engine:
         results[i].out_len bytes long; results as deflate_stream_jobs.  Asynchronous: results_to_host(results, STREAM_RESULT_DTYPE)."""
         return self._deflate_streams(fc, fmt, None, bufs, hist_max, level)
 
+    # ---- ... with the streams' checkpoint index written on the way ----
+    def deflate_stream_jobs_indexed(self, fc, fmt, jobs, span, cp_cap, windows=True, index_jobs=True, results=None, hist_max=0, level=-1,
+                                    cbit=None, uoff=None, streams=None):
+        """nxz_batch_deflate_streams_indexed: deflate_stream_jobs that also writes the checkpoint index of every stream, in the shapes
+        checkpoint_read_ranges_batch takes.  Returns (rc, results, cbit, uoff, windows, streams, index_jobs): cbit / uoff int64
+        device tensors of shape (n, cp_cap + 1); windows a uint8 device tensor of shape (n, cp_cap, 32768) (True, or a tensor to
+        write to; False / None: positions only, None returned); streams a uint8 device tensor of n CHECKPOINT_STREAM_DTYPE records;
+        index_jobs a uint8 device tensor of n JOB_DTYPE records, the reader's jobs (True, or a tensor; False / None: none).  Any
+        of cbit, uoff, streams may be passed as a tensor to write to, or as False for NULL (which the call refuses).
+        Asynchronous on torch's current stream."""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, STREAM_JOB_DTYPE)
+        n = len(jobs)
+        if results is None:
+            results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if cbit is None:
+            cbit = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if uoff is None:
+            uoff = t.zeros((max(n, 1), cp_cap + 1), dtype=t.int64, device=self.dev)
+        if windows is True:
+            windows = t.zeros((max(n, 1), cp_cap, CHECKPOINT_WINDOW), dtype=t.uint8, device=self.dev)
+        if streams is None:
+            streams = t.zeros(max(n, 1) * CHECKPOINT_STREAM_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        if index_jobs is True:
+            index_jobs = t.zeros(max(n, 1) * JOB_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+
+        def ptr(x):
+            return x.data_ptr() if x is not None and x is not False else None
+        rc = self.L.nxz_batch_deflate_streams_indexed(self.ctx, fc, fmt, level, hist_max, jobs.ctypes.data if n else None, n, results.data_ptr(),
+                                                      span, cp_cap, ptr(cbit), ptr(uoff), ptr(windows), ptr(streams), ptr(index_jobs),
+                                                      self.stream_handle())
+        return rc, results, cbit, uoff, (windows if ptr(windows) else None), streams, (index_jobs if ptr(index_jobs) else None)
+
+    def deflate_streams_indexed(self, fc, fmt, bufs, span, cp_cap, windows=True, hist_max=0, level=-1):
+        """deflate_streams with the checkpoint index of every stream: a checkpoint at the first block header behind every `span`
+        bytes of source, cp_cap of them stored per stream at most.  Returns (out, offsets, results, cbit, uoff, windows, streams,
+        index_jobs): the first three as deflate_streams, the rest as deflate_stream_jobs_indexed -- what
+        checkpoint_read_ranges_batch(index_jobs, len(bufs), cp_cap, cbit, uoff, None, windows, streams, ranges) takes, with no
+        host step in between."""
+        j, out, offsets = self._stream_jobs(None, bufs, hist_max, fmt)
+        rc, results, cbit, uoff, windows, streams, index_jobs = self.deflate_stream_jobs_indexed(fc, fmt, j, span, cp_cap, windows=windows,
+                                                                                                 hist_max=hist_max, level=level)
+        self._check(rc, "nxz_batch_deflate_streams_indexed")
+        return out, offsets, results, cbit, uoff, windows, streams, index_jobs
+
     # ---- ... with one preset dictionary as the window of every stream's first block ----
     def deflate_stream_bound_dict(self, src_len, hist_max=0, fmt=FMT_ZLIB):
         """nxz_deflate_stream_bound_dict: the dst_cap a buffer of src_len bytes needs (FMT_RAW / FMT_ZLIB; 0 for FMT_GZIP)"""
@@ -493,7 +541,8 @@ class Engine:
         bytes -- none at hist_max 0, where the stream only names the dictionary (FMT_RAW / FMT_ZLIB)"""
         return self._deflate_streams(fc, fmt, d, bufs, hist_max, level)
 
-    def _deflate_streams(self, fc, fmt, d, bufs, hist_max, level):
+    def _stream_jobs(self, d, bufs, hist_max, fmt):
+        """the STREAM_JOB_DTYPE records of bufs, their targets in one device tensor `out` at `offsets` -> (jobs, out, offsets)"""
         t = self.torch
         j = np.zeros(len(bufs), STREAM_JOB_DTYPE)
         bound = self.deflate_stream_bound if d is None else self.deflate_stream_bound_dict
@@ -504,6 +553,10 @@ class Engine:
         for i, b in enumerate(bufs):
             assert b.dtype == t.uint8 and b.is_contiguous() and b.device == out.device
             j[i] = (b.data_ptr() if b.numel() else 0, out.data_ptr() + int(offsets[i]), b.numel(), caps[i])
+        return j, out, offsets
+
+    def _deflate_streams(self, fc, fmt, d, bufs, hist_max, level):
+        j, out, offsets = self._stream_jobs(d, bufs, hist_max, fmt)
         if d is None:
             rc, results = self.deflate_stream_jobs(fc, fmt, j, hist_max=hist_max, level=level)
         else:
