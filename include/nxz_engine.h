@@ -765,6 +765,67 @@ int nxz_batch_deflate_streams_dict(nxz_ctx_t *ctx, int fc, int fmt, int level, u
 				   const nxz_stream_job_t *jobs /* HOST */, size_t n,
 				   nxz_stream_result_t *results /* DEVICE */, void *stream);
 
+/* A stream WRITTEN IN PARTS: the source of stream i arrives over several calls (a shard that grows, a tensor stream written layer
+ * by layer, a file larger than what is resident), each call compresses the part it is given and appends to nothing -- the bytes of
+ * THIS part go to jobs[i].dst and the caller lays the parts' out_len bytes end to end.  What a stream carries from call to call is
+ * carry[i] (DEVICE, read and written by the device: a later call may be queued behind an earlier one with no host step between)
+ * and the source bytes just in front of the part, which the caller keeps or leaves where they are.  Everything not named here is
+ * nxz_batch_deflate_streams's: fc, fmt, level, hist_max and its rounding, NXZ_STREAMS_CHUNK, the error returns, the asynchrony.
+ * The block plan of a part is the plan of a buffer: H = hist_max rounded, B = 65536 - H, block k starts at k * B and, for k >= 1,
+ * sees the H bytes of its own part in front of it.  Block 0 sees the last h0 = min(H, prev_len) & ~15 bytes of `prev` -- the `prev`
+ * rule of nxz_deflate_host_hist, which nxz_batch_deflate_streams_dict restates for its dictionary; h0 == 0: no window.  The
+ * deflate data of a part is byte for byte what nxz_deflate_host_hist(fc, src, src_len, final = LAST, hist_max, prev, prev_len)
+ * writes: a part without NXZ_PART_LAST carries no BFINAL and ends on a byte boundary (the empty stored block behind a last block
+ * that ends inside a byte), so the stream written so far inflates to every source byte so far; a part of length 0 writes no
+ * deflate data without LAST and 01 00 00 ff ff with it.
+ *   NXZ_PART_FIRST   the plain call's header in front (0, 2 or 10 bytes); the incoming carry[i] is ignored and started afresh
+ *   NXZ_PART_LAST    the plain call's trailer behind, from the carry: the Adler-32 or the CRC-32 of all parts, ISIZE = total_in
+ *                    mod 2^32; carry[i].status = 1
+ * dst_cap >= nxz_deflate_stream_part_bound(src_len, hist_max, fmt, flags) = src_len + 10 a block + 16, the header with FIRST, the
+ * trailer with LAST.  results[i]: out_len = this part's bytes at dst, blocks and stored count this part's blocks, crc and adler
+ * are the running values of the whole stream through this part (the carry's).  For a job with FIRST | LAST the bytes at dst and
+ * results[i] are exactly what nxz_batch_deflate_streams writes for the same arguments.
+ * Refused (results[i].cc; dst and carry[i] untouched, the neighbours unaffected, the part may be sent again): the plain call's
+ * refusals against this bound (NXZ_CC_TARGET_SPACE: out_len = the bound), and NXZ_CC_INVALID_OP for prev == NULL with
+ * prev_len != 0, flag bits other than the two, FIRST with prev_len != 0 (a preset window on a stream's first part is the
+ * dictionary call's job), no FIRST on a carry whose status != 0.
+ * Where the window comes from: with prev + prev_len == src (the parts lie one behind the other in memory) block 0's compress job
+ * simply begins h0 bytes in front of src and nothing is copied.  Otherwise a kernel of its own stages [window][block 0] in 64 KiB
+ * of the stream's scratch per such block of a chunk -- 16 bytes a lane, the window from any alignment through aligned loads
+ * joined by a byte shift -- and the job reads from there.  On the device: power-gzip_amd/csrc/nxz_streams_part.hip, the rules in
+ * nxz_streams_part.h; which blocks are staged the host knows from its one pass over the streams.
+ * Asynchronous on `stream`: no host wait and no allocation once the stream's scratch has grown.  Returns as
+ * nxz_batch_deflate_streams, and -EINVAL for carry == NULL with n > 0.
+ * Not part of this call: the dictionary form; the indexed form; carrying a partly filled byte from part to part (a part always
+ * ends on a byte boundary: up to five bytes a part more than one call on the whole source writes); nx_deflate on top of it.
+ * Speed (tools/bench_streams_part.py, profiles/r24_streams_part.txt; zlib, DHTGEN, 4096 streams of 1 MiB, medians of 5 runs taken in
+ * turn, every route within 0.2 % of its median): one FIRST | LAST part 1.002 (hist_max 0) and 1.001 (32768) of the time of
+ * nxz_batch_deflate_streams (41.79 against 41.70 ms, 54.56 against 54.51) -- inside that call's own spread.  A stream in 4 parts of
+ * 256 KiB, a call a part: 1.006 / 1.008 with the parts contiguous, 1.007 / 1.017 with prev detached (every part's first block staged);
+ * in 16 parts of 64 KiB: 1.019 / 1.022 contiguous, 1.020 / 1.053 detached (57.4 against 54.5 ms: with hist_max 32768 every second
+ * block of the batch is staged). */
+enum { NXZ_PART_FIRST = 1u, NXZ_PART_LAST = 2u };
+typedef struct nxz_stream_part_job {   /* HOST array */
+	const uint8_t *src;            /* DEVICE, 16-byte aligned: this part's source */
+	uint8_t       *dst;            /* DEVICE, any alignment: where THIS part's bytes go (the caller appends them to the stream) */
+	uint64_t       src_len;        /* any length, 0 included */
+	uint64_t       dst_cap;        /* >= nxz_deflate_stream_part_bound(src_len, hist_max, fmt, flags) */
+	const uint8_t *prev;           /* DEVICE or NULL, any alignment: the prev_len source bytes of the stream just in front of this part */
+	uint32_t       prev_len;       /* any value; only the tail counts (above) */
+	uint32_t       flags;          /* NXZ_PART_FIRST | NXZ_PART_LAST */
+} nxz_stream_part_job_t;
+typedef struct nxz_stream_carry {      /* DEVICE, 32 bytes, one per stream, read and written by the device */
+	uint32_t crc, adler;           /* of all source bytes so far, from 0 / 1 */
+	uint64_t total_in, total_out;  /* source bytes taken / stream bytes written so far, framing included */
+	uint32_t parts;                /* parts taken, empty ones included */
+	uint32_t status;               /* 0 open, 1 finished */
+} nxz_stream_carry_t;
+size_t nxz_deflate_stream_part_bound(uint64_t src_len, uint32_t hist_max, int fmt, uint32_t flags);
+int nxz_batch_deflate_streams_part(nxz_ctx_t *ctx, int fc, int fmt, int level, uint32_t hist_max,
+				   const nxz_stream_part_job_t *jobs /* HOST */, size_t n,
+				   nxz_stream_carry_t *carry /* DEVICE, n, in/out */,
+				   nxz_stream_result_t *results /* DEVICE, n */, void *stream);
+
 /* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */

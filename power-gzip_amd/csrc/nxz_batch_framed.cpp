@@ -5,6 +5,7 @@
 #include "nxz_ctx.h"
 #include "nxz_streams_dict.h"
 #include "nxz_streams_index.h"
+#include "nxz_streams_part.h"
 #include "nxz_checkpoint_fine.h"
 #include "nxz_checkpoint_batch.h"
 
@@ -221,6 +222,34 @@ extern "C" size_t nxz_deflate_stream_bound_dict(uint64_t src_len, uint32_t hist_
 	return nxz_streams_dict_fmt_ok(fmt) ? (size_t)nxz_streams_dict_bound(src_len, hist_max, fmt) : 0;
 }
 
+// This call's pinned staging of `up_bytes` (Scratch::h_up: two in turn): the upload that read it last must have run.  0 and *h, *ev
+// (to record behind this call's upload: streams_upload), or -errno.
+static int streams_staging(nxz_ctx_t *c, hipStream_t s, size_t up_bytes, uint8_t **h, hipEvent_t *ev)
+{
+	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
+	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
+	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), return -ENOMEM);
+	else HIPCHK(hipEventSynchronize(st.ev), return -EIO);
+	if (st.cap < up_bytes) {
+		if (st.h) (void)hipHostFree(st.h);
+		st.h = nullptr; st.cap = 0;
+		if (hipHostMalloc((void **)&st.h, up_bytes) == hipSuccess) st.cap = up_bytes;
+		else { (void)hipGetLastError(); st.h = nullptr; }
+	}
+	with_scratch(c, s, [&](nxz_ctx::Scratch &r) { r.h_up[st.k] = st.h; r.h_up_cap[st.k] = st.cap; r.up_ev[st.k] = st.ev; return 0; });
+	if (!st.h) return -ENOMEM;
+	*h = st.h; *ev = st.ev;
+	return 0;
+}
+// ... and its upload to `d`, queued on `s`
+static int streams_upload(nxz_ctx_t *c, hipStream_t s, uint8_t *d, const uint8_t *h, size_t up_bytes, hipEvent_t ev)
+{
+	HIPCHK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
+	HIPCHK(hipEventRecord(ev, s), return -EIO);
+	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
+	return 0;
+}
+
 // what nxz_batch_deflate_streams_indexed adds to a call: the caller's arrays (its arguments, checked there)
 struct StreamsIndex {
 	uint64_t span;
@@ -251,23 +280,14 @@ static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hi
 	// what is uploaded: [descriptors][first]([nz]), the same layout in the staging and in the device buffer
 	const size_t o_first = up(n * sizeof(nxz_stream_job_t)), o_nz = o_first + up((n + 1) * sizeof(uint32_t)),
 		     up_bytes = split ? o_nz + (n + 1) * sizeof(uint32_t) : o_first + (n + 1) * sizeof(uint32_t);
-	// this call's staging: the upload that read it last must have run
-	struct Staging { uint8_t *h; size_t cap; hipEvent_t ev; unsigned k; };
-	Staging st = with_scratch(c, s, [](nxz_ctx::Scratch &r) { const unsigned k = r.up_turn & 1; return Staging{r.h_up[k], r.h_up_cap[k], r.up_ev[k], k}; });
-	if (!st.ev) HIPCHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming), return -ENOMEM);
-	else HIPCHK(hipEventSynchronize(st.ev), return -EIO);
-	if (st.cap < up_bytes) {
-		if (st.h) (void)hipHostFree(st.h);
-		st.h = nullptr; st.cap = 0;
-		if (hipHostMalloc((void **)&st.h, up_bytes) == hipSuccess) st.cap = up_bytes;
-		else { (void)hipGetLastError(); st.h = nullptr; }
-	}
-	with_scratch(c, s, [&](nxz_ctx::Scratch &r) { r.h_up[st.k] = st.h; r.h_up_cap[st.k] = st.cap; r.up_ev[st.k] = st.ev; return 0; });
-	if (!st.h) return -ENOMEM;
+	uint8_t *st_h = nullptr;
+	hipEvent_t st_ev = nullptr;
+	int rc = streams_staging(c, s, up_bytes, &st_h, &st_ev);
+	if (rc) return rc;
 	// one pass over the streams: a refused stream gets no blocks
-	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st.h;
-	uint32_t *const h_first = (uint32_t *)(st.h + o_first);
-	uint32_t *const h_nz = split ? (uint32_t *)(st.h + o_nz) : nullptr;   // the streams with blocks in front of each stream
+	nxz_stream_job_t *const h_desc = (nxz_stream_job_t *)st_h;
+	uint32_t *const h_first = (uint32_t *)(st_h + o_first);
+	uint32_t *const h_nz = split ? (uint32_t *)(st_h + o_nz) : nullptr;   // the streams with blocks in front of each stream
 	memcpy(h_desc, jobs, n * sizeof(nxz_stream_job_t));
 	uint64_t total = 0;
 	uint32_t with_blocks = 0;
@@ -310,10 +330,8 @@ static int deflate_streams(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hi
 	uint32_t *const d_pos = split ? (uint32_t *)(d + o_pos) : nullptr;
 	nxz_stream_index_state_t *const d_ist = ix ? (nxz_stream_index_state_t *)(d + o_ist) : nullptr;
 	uint32_t *const d_marks = ix && ix->windows ? (uint32_t *)(d + o_marks) : nullptr;
-	HIPCHK(hipMemcpyAsync(d, st.h, up_bytes, hipMemcpyHostToDevice, s), return -EIO);
-	HIPCHK(hipEventRecord(st.ev, s), return -EIO);
-	with_scratch(c, s, [](nxz_ctx::Scratch &r) { r.up_turn++; return 0; });
-	int rc = launched("streams prologue launch", dict ? nxz_launch_streams_dict_prologue(d_desc, ns, hist_max, fmt, level, dict->id, d_state, s)
+	if ((rc = streams_upload(c, s, d, st_h, up_bytes, st_ev)) != 0) return rc;
+	rc = launched("streams prologue launch", dict ? nxz_launch_streams_dict_prologue(d_desc, ns, hist_max, fmt, level, dict->id, d_state, s)
 							  : nxz_launch_streams_prologue(d_desc, ns, hist_max, fmt, level, d_state, s));
 	if (rc) return rc;
 	if (ix && (rc = launched("streams index prologue launch", nxz_launch_streams_index_prologue(d_desc, ns, fmt, d_state, ix->cp_cap, ix->cbit, ix->uoff,
@@ -377,6 +395,95 @@ extern "C" int nxz_batch_deflate_streams_dict(nxz_ctx_t *c, int fc, int fmt, int
 {
 	if (!c || !dict || dict->device != c->device) return -EINVAL;
 	return deflate_streams(c, fc, fmt, level, hist_max, dict, jobs, n, results, stream);
+}
+
+// ---------------------------------------------------------------------------
+// A stream written in parts (nxz_streams_part.hip, the rules in nxz_streams_part.h): deflate_streams' shape with the part's kernels --
+// the same pinned staging and upload, the same chunk loop, BUF_STREAMS under frame_use[s], everything on `s` and no host wait.  The
+// host's one pass also counts the parts whose first block is STAGED (a window that does not lie in front of the source in memory):
+// sg[] goes up beside first[], and per chunk the host knows how many staging slots its first blocks take and how many lie in front
+// of it.  The slots (65 536 bytes a staged block of a chunk) and the chunk's staging list lie behind the plain call's layout.
+// What the host cannot see is the carry: a part without FIRST on a finished stream is planned like any other and refused on the device.
+// ---------------------------------------------------------------------------
+extern "C" size_t nxz_deflate_stream_part_bound(uint64_t src_len, uint32_t hist_max, int fmt, uint32_t flags)
+{
+	return (size_t)nxz_streams_part_bound(src_len, hist_max, fmt, flags);
+}
+
+extern "C" int nxz_batch_deflate_streams_part(nxz_ctx_t *c, int fc, int fmt, int level, uint32_t hist_max, const nxz_stream_part_job_t *jobs, size_t n,
+					      nxz_stream_carry_t *carry, nxz_stream_result_t *results, void *stream)
+{
+	if (!c || (fc != NXZ_FC_COMPRESS_FHT && fc != NXZ_FC_COMPRESS_DHTGEN) || !nxz_streams_fmt_ok(fmt) || level < -1 || level > 9 ||
+	    (n && (!jobs || !results || !carry))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	if (n >= (1u << 31)) return -E2BIG;
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint32_t H = nxz_streams_window(hist_max), B = nxz_streams_block_bytes(hist_max), ns = (uint32_t)n;
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	// what is uploaded: [descriptors][first][sg], the same layout in the staging and in the device buffer
+	const size_t o_first = up(n * sizeof(nxz_stream_part_job_t)), o_sg = o_first + up((n + 1) * sizeof(uint32_t)), up_bytes = o_sg + (n + 1) * sizeof(uint32_t);
+	uint8_t *st_h = nullptr;
+	hipEvent_t st_ev = nullptr;
+	int rc = streams_staging(c, s, up_bytes, &st_h, &st_ev);
+	if (rc) return rc;
+	// one pass over the streams: a part the host refuses gets no blocks; a part with blocks may have its first one staged
+	uint32_t *const h_first = (uint32_t *)(st_h + o_first), *const h_sg = (uint32_t *)(st_h + o_sg);
+	memcpy(st_h, jobs, n * sizeof(nxz_stream_part_job_t));
+	uint64_t total = 0;
+	uint32_t staged = 0;
+	for (size_t i = 0; i < n; i++) {
+		h_first[i] = (uint32_t)total;
+		h_sg[i] = staged;
+		if (nxz_streams_part_refusal(&jobs[i], 0, hist_max, fmt)) continue;
+		total += nxz_streams_blocks(jobs[i].src_len, B);
+		if (total >= (1ull << 31)) return -E2BIG;
+		if (nxz_streams_part_staged(&jobs[i], hist_max)) staged++;
+	}
+	h_first[n] = (uint32_t)total;
+	h_sg[n] = staged;
+	const uint32_t nblk = (uint32_t)total, C = std::min(streams_chunk(), nblk), S = std::min(C, staged);   // S: the staged blocks a chunk holds at most
+	const size_t o_state = up(up_bytes), o_jobs = o_state + up(n * sizeof(nxz_stream_state_t)), o_res = o_jobs + up((size_t)C * sizeof(nxz_batch_job_t)),
+		     o_owner = o_res + up((size_t)C * sizeof(nxz_batch_result_t)), o_off = o_owner + up((size_t)C * sizeof(uint32_t)),
+		     o_slots = o_off + up((size_t)C * sizeof(uint64_t)), o_list = o_slots + up((size_t)C * NXZ_STREAMS_SLOT),
+		     o_stage = o_list + up((size_t)S * sizeof(uint32_t)), d_bytes = o_stage + (size_t)S * NXZ_STREAMS_STAGE_SLOT;
+	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
+		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
+		return r.buf[BUF_STREAMS].p;
+	});
+	if (!d) return -ENOMEM;
+	const nxz_stream_part_job_t *const d_desc = (const nxz_stream_part_job_t *)d;
+	const uint32_t *const d_first = (const uint32_t *)(d + o_first), *const d_sg = (const uint32_t *)(d + o_sg);
+	nxz_stream_state_t *const d_state = (nxz_stream_state_t *)(d + o_state);
+	nxz_batch_job_t *const d_jobs = (nxz_batch_job_t *)(d + o_jobs);
+	nxz_batch_result_t *const d_res = (nxz_batch_result_t *)(d + o_res);
+	uint32_t *const d_owner = (uint32_t *)(d + o_owner), *const d_list = (uint32_t *)(d + o_list);
+	uint64_t *const d_off = (uint64_t *)(d + o_off);
+	uint8_t *const d_slots = d + o_slots, *const d_stage = d + o_stage;
+	if ((rc = streams_upload(c, s, d, st_h, up_bytes, st_ev)) != 0) return rc;
+	if ((rc = launched("streams part prologue launch", nxz_launch_streams_part_prologue(d_desc, ns, hist_max, fmt, level, carry, d_state, s))) != 0) return rc;
+	const uint32_t op_block = nxz_crc_shift_op(B);
+	uint32_t i_lo = 0;                                                  // the stream of the chunk's first block (the chunks go in order)
+	for (uint32_t b0 = 0; b0 < nblk; b0 += C) {
+		const uint32_t m = std::min(C, nblk - b0);
+		while (h_first[i_lo + 1] <= b0) i_lo++;
+		uint32_t i_hi = i_lo;
+		while (h_first[i_hi + 1] < b0 + m) i_hi++;
+		// the staged first blocks in front of the chunk and inside it (i_lo owns b0: its first block lies in front unless it IS b0;
+		// i_hi owns b0 + m - 1: its first block is not behind the chunk)
+		const uint32_t sg_b0 = h_first[i_lo] < b0 ? h_sg[i_lo + 1] : h_sg[i_lo], nst = h_sg[i_hi + 1] - sg_b0;
+		rc = nxz_launch_streams_part_expand(d_desc, d_first, d_sg, ns, b0, m, hist_max, sg_b0, d_slots, d_stage, d_jobs, d_owner, d_list, s);
+		if (!rc && nst) rc = nxz_launch_streams_part_stage(d_desc, d_owner, d_list, nst, d_jobs, s);
+		if ((rc = launched("streams part expand launch", rc)) != 0) return rc;
+		if ((rc = nxz_batch_compress(c, fc | (H ? 0x08 : 0), d_jobs, m, nullptr, 0, d_res, nullptr, s)) != 0) return rc;
+		rc = nxz_launch_streams_part_layout(d_desc, d_first, i_lo, i_hi - i_lo + 1, b0, m, d_jobs, d_res, hist_max, op_block, d_state, d_off, s);
+		if (!rc) rc = nxz_launch_streams_part_pack(d_desc, d_first, d_owner, b0, m, d_jobs, d_res, d_off, d_state, s);
+		if ((rc = launched("streams part pack launch", rc)) != 0) return rc;
+		i_lo = i_hi;
+	}
+	return launched("streams part epilogue launch", nxz_launch_streams_part_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, carry, results, s));
 }
 
 // The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then

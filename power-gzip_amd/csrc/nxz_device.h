@@ -256,6 +256,25 @@ int nxz_launch_streams_index_windows(const nxz_stream_job_t *desc, const uint32_
 int nxz_launch_streams_index_epilogue(const nxz_stream_job_t *desc, uint32_t n, int fmt, const nxz_stream_result_t *results,
 				      const nxz_stream_index_state_t *ist, uint32_t cp_cap, uint64_t *cbit, uint64_t *uoff,
 				      nxz_checkpoint_stream_t *streams, nxz_batch_job_t *index_jobs, hipStream_t stream);
+/* nxz_streams_part.hip: a stream written in parts, a device buffer a part (nxz_batch_deflate_streams_part; nxz_streams_part.h has the
+ * rules).  The plain call's launches with the part's descriptors and the streams' carry records, and the staging of first blocks whose
+ * window does not lie in front of them in memory: sg[n + 1]: the staged parts in front of each stream; sg_b0: the staged first blocks
+ * in front of the chunk; stage: 65 536 bytes a staged block of the chunk; staged[q]: the chunk's q-th staged block (indexed from b0) */
+int nxz_launch_streams_part_prologue(const nxz_stream_part_job_t *desc, uint32_t n, uint32_t hist_max, int fmt, int level,
+				     const nxz_stream_carry_t *carry, nxz_stream_state_t *state, hipStream_t stream);
+int nxz_launch_streams_part_expand(const nxz_stream_part_job_t *desc, const uint32_t *first, const uint32_t *sg, uint32_t n, uint32_t b0,
+				   uint32_t m, uint32_t hist_max, uint32_t sg_b0, uint8_t *slots, uint8_t *stage, nxz_batch_job_t *jobs,
+				   uint32_t *owner, uint32_t *staged, hipStream_t stream);
+int nxz_launch_streams_part_stage(const nxz_stream_part_job_t *desc, const uint32_t *owner, const uint32_t *staged, uint32_t ns,
+				  const nxz_batch_job_t *jobs, hipStream_t stream);
+int nxz_launch_streams_part_layout(const nxz_stream_part_job_t *desc, const uint32_t *first, uint32_t i_lo, uint32_t streams, uint32_t b0,
+				   uint32_t m, const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, uint32_t hist_max,
+				   uint32_t op_block, nxz_stream_state_t *state, uint64_t *offsets, hipStream_t stream);
+int nxz_launch_streams_part_pack(const nxz_stream_part_job_t *desc, const uint32_t *first, const uint32_t *owner, uint32_t b0, uint32_t m,
+				 const nxz_batch_job_t *jobs, const nxz_batch_result_t *results, const uint64_t *offsets,
+				 const nxz_stream_state_t *state, hipStream_t stream);
+int nxz_launch_streams_part_epilogue(const nxz_stream_part_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
+				     const nxz_stream_state_t *state, nxz_stream_carry_t *carry, nxz_stream_result_t *results, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

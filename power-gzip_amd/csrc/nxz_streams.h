@@ -129,8 +129,9 @@ NXZ_STREAMS_HD inline uint32_t nxz_gf2_pow32(uint32_t base, uint64_t e)
 NXZ_STREAMS_HD inline uint32_t nxz_crc_shift_op(uint64_t nbytes) { return nxz_gf2_pow32(0x00800000u, nbytes); }
 /* crc of [a][b]: crc_a moved over b's bytes (op = nxz_crc_shift_op(len_b), or a product of such), then crc_b */
 NXZ_STREAMS_HD inline uint32_t nxz_crc_join(uint32_t crc_a, uint32_t crc_b, uint32_t op) { return nxz_gf2_mul32(crc_a, op) ^ crc_b; }
-/* the operator of `full` blocks of B bytes each (op_block = nxz_crc_shift_op(B), made once) and `tail` bytes more */
-NXZ_STREAMS_HD inline uint32_t nxz_crc_blocks_op(uint32_t op_block, uint64_t full, uint32_t tail)
+/* the operator of `full` blocks of B bytes each (op_block = nxz_crc_shift_op(B), made once) and `tail` bytes more
+ * (always inlined: left as a call it costs the layout kernels, its one user on the device, the eighth wavefront a SIMD) */
+NXZ_STREAMS_HD inline __attribute__((always_inline)) uint32_t nxz_crc_blocks_op(uint32_t op_block, uint64_t full, uint32_t tail)
 {
 	const uint32_t f = nxz_gf2_pow32(op_block, full);
 	return tail ? nxz_gf2_mul32(f, nxz_crc_shift_op(tail)) : f;

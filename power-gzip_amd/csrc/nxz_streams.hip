@@ -39,82 +39,12 @@ __global__ __launch_bounds__(256) void expand_kernel(const nxz_stream_job_t *__r
 	owner[t] = i;
 }
 
-__device__ inline uint32_t wave_xor(uint32_t v)
-{
-	for (int d = 32; d; d >>= 1) v ^= __shfl_xor(v, d);
-	return v;
-}
-__device__ inline uint64_t wave_sum(uint64_t v)
-{
-	for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-	return v;
-}
-
-// One wavefront per stream of [i_lo, i_lo + gridDim.x); the stream's blocks inside the chunk [b0, b0 + m), 64 at a time, a lane each.
-// Sizes and the Adler sums are prefix sums over the lanes.  The CRC needs no scan: every block but a stream's last has B bytes, so
-// a lane knows how many bytes lie behind its block in this part and moves its block's CRC over them itself (op_block = the operator
-// of B bytes, made once by the host; powers of it by square-and-multiply); the moved CRCs are XORed together.
+// One wavefront per stream of [i_lo, i_lo + gridDim.x): layout_stream (nxz_streams_dev.h); a stream's last block is the final one.
 __global__ __launch_bounds__(64) void layout_kernel(const uint32_t *__restrict__ first, uint32_t i_lo, uint32_t b0, uint32_t m,
 						      const nxz_batch_job_t *__restrict__ jobs, const nxz_batch_result_t *__restrict__ results,
 						      uint32_t B, uint32_t op_block, nxz_stream_state_t *__restrict__ state, uint64_t *__restrict__ offsets)
 {
-	const uint32_t i = i_lo + blockIdx.x, lane = threadIdx.x;
-	const uint32_t f0 = first[i], f1 = first[i + 1];
-	const uint32_t lo = f0 > b0 ? f0 : b0, hi = f1 < b0 + m ? f1 : b0 + m;
-	if (lo >= hi) return;
-	const nxz_stream_state_t st = state[i];
-	const uint32_t M = NXZ_ADLER_BASE;
-	// the part's last block: the only one that may be short
-	const uint32_t last_len = jobs[hi - 1 - b0].src_len - jobs[hi - 1 - b0].hist_len;
-	const uint32_t tail = last_len == B ? 0 : last_len, last_full = last_len == B ? 1 : 0;
-	uint64_t base = st.written, adler_b = 0;
-	uint32_t base_da = ((st.adler & 0xffff) + M - 1) % M;                 // (Adler's low sum so far) - 1
-	uint32_t crc_part = 0, stored = 0;
-	for (uint32_t i0 = lo; i0 < hi; i0 += 64) {
-		const uint32_t g = i0 + lane;
-		const bool valid = g < hi;
-		uint32_t size = 0, da = 0, len = 0, crc = 0, bsum = 0;
-		bool is_stored = false;
-		if (valid) {
-			const nxz_batch_job_t job = jobs[g - b0];
-			const nxz_batch_result_t r = results[g - b0];
-			const nxz::StreamPiece p = nxz::stream_piece(job, r, g == f1 - 1);
-			size = p.size; len = p.len; is_stored = p.stored;
-			crc = r.crc; da = ((r.adler & 0xffff) + M - 1) % M; bsum = r.adler >> 16;
-		}
-		uint64_t incl = size;
-		uint32_t incl_da = da;
-		for (uint32_t d = 1; d < 64; d <<= 1) {
-			const uint64_t v = __shfl_up(incl, d);
-			const uint32_t w = __shfl_up(incl_da, d);
-			if (lane >= d) { incl += v; incl_da += w; }
-		}
-		if (valid) {
-			offsets[g - b0] = base + incl - size;
-			// the bytes behind this block in the part: hi - 1 - g blocks, all of B bytes but perhaps the last
-			const uint32_t behind = hi - 1 - g;
-			const uint32_t op = behind ? nxz_crc_blocks_op(op_block, (uint64_t)behind - 1 + last_full, tail) : 0x80000000u;
-			crc_part ^= nxz_gf2_mul32(crc, op);
-			const uint32_t P = (base_da + incl_da - da) % M;              // (the low sum in front of this block) - 1
-			adler_b += (bsum + (uint64_t)(len % M) * P) % M;
-		}
-		base += __shfl(incl, 63);
-		base_da = (base_da + __shfl(incl_da, 63)) % M;
-		stored += (uint32_t)__popcll(__ballot(valid && is_stored));
-	}
-	crc_part = wave_xor(crc_part);
-	adler_b = wave_sum(adler_b);
-	if (lane == 0) {
-		const uint32_t cnt = hi - lo;
-		const uint64_t bytes = (uint64_t)(cnt - 1) * B + last_len;
-		nxz_stream_state_t o = st;
-		o.written = base;
-		o.len_done = st.len_done + bytes;
-		o.crc = nxz_crc_join(st.crc, crc_part, nxz_crc_blocks_op(op_block, (uint64_t)cnt - 1 + last_full, tail));
-		o.adler = (uint32_t)(((st.adler >> 16) + adler_b) % M) << 16 | (base_da + 1) % M;
-		o.stored = st.stored + stored;
-		state[i] = o;
-	}
+	layout_stream(first, i_lo + blockIdx.x, b0, m, jobs, results, B, op_block, state, offsets, true);
 }
 
 __global__ __launch_bounds__(256) void pack_kernel(const nxz_stream_job_t *__restrict__ desc, const uint32_t *__restrict__ first,

@@ -48,6 +48,12 @@ STREAM_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u8"),
 STREAM_RESULT_DTYPE = np.dtype([("cc", "<u4"), ("blocks", "<u4"), ("out_len", "<u8"), ("crc", "<u4"), ("adler", "<u4"),
                                 ("stored", "<u4"), ("reserved", "<u4")])
 assert STREAM_JOB_DTYPE.itemsize == 32 and STREAM_RESULT_DTYPE.itemsize == 32
+# a stream written in parts (include/nxz_engine.h: nxz_batch_deflate_streams_part)
+PART_FIRST, PART_LAST = 1, 2
+STREAM_PART_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<u8"), ("dst_cap", "<u8"), ("prev", "<u8"), ("prev_len", "<u4"),
+                                  ("flags", "<u4")])
+STREAM_CARRY_DTYPE = np.dtype([("crc", "<u4"), ("adler", "<u4"), ("total_in", "<u8"), ("total_out", "<u8"), ("parts", "<u4"), ("status", "<u4")])
+assert STREAM_PART_JOB_DTYPE.itemsize == 48 and STREAM_CARRY_DTYPE.itemsize == 32
 
 # multi-member gzip jobs (include/nxz_engine.h: nxz_batch_gzip_members_size / _decode)
 GZIP_MEMBER_DTYPE = np.dtype([("uoff", "<u8"), ("coff", "<u4"), ("clen", "<u4"), ("hdr_len", "<u4"), ("isize", "<u4"),
@@ -192,6 +198,10 @@ def load_library():
                                                         C.c_void_p]
         L.nxz_deflate_stream_bound_dict.argtypes = [C.c_uint64, C.c_uint32, C.c_int]
         L.nxz_batch_deflate_streams_dict.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_void_p]
+        L.nxz_deflate_stream_part_bound.restype = C.c_size_t
+        L.nxz_deflate_stream_part_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]
+        L.nxz_batch_deflate_streams_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
@@ -467,6 +477,24 @@ class Engine:
             results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
         rc = self.L.nxz_batch_deflate_streams(self.ctx, fc, fmt, level, hist_max, jobs.ctypes.data if n else None, n, results.data_ptr(),
                                               self.stream_handle())
+        return rc, results
+
+    def deflate_stream_part_bound(self, src_len, hist_max=0, fmt=FMT_ZLIB, flags=PART_FIRST | PART_LAST):
+        """nxz_deflate_stream_part_bound: the dst_cap a part of src_len bytes needs"""
+        return self.L.nxz_deflate_stream_part_bound(src_len, hist_max, fmt, flags)
+
+    def deflate_stream_parts(self, fc, fmt, jobs, carry, results=None, hist_max=0, level=-1):
+        """nxz_batch_deflate_streams_part on a HOST array of STREAM_PART_JOB_DTYPE records (device addresses): a part of a stream each.
+        carry: a uint8 device tensor of len(jobs) STREAM_CARRY_DTYPE records, read and written by the device (None is passed on as
+        NULL, which the call refuses); results_to_host(carry, STREAM_CARRY_DTYPE) reads it.  Returns (rc, results) as
+        deflate_stream_jobs.  Asynchronous on torch's current stream: the next part may be queued without a wait in between."""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, STREAM_PART_JOB_DTYPE)
+        n = len(jobs)
+        if results is None:
+            results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_deflate_streams_part(self.ctx, fc, fmt, level, hist_max, jobs.ctypes.data if n else None, n,
+                                                   carry.data_ptr() if carry is not None else None, results.data_ptr(), self.stream_handle())
         return rc, results
 
     def deflate_streams(self, fc, fmt, bufs, hist_max=0, level=-1):
