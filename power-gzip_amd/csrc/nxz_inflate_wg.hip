@@ -93,6 +93,7 @@ struct __attribute__((aligned(16))) Lds {
 	uint32_t wb, wbits, wend, wvalid, aoff, fl0, lowest, inblock, act, cut, stall, done;
 	// the header's code lengths by all wavefronts (read_lengths): every segment's first bit and what stands in front of it; the walk's state
 	uint32_t segin[NW], hstate, hn, hprev, hein, hend, hpos;
+	uint32_t hbad;                      // wavefront 0 refuses the dynamic header: L.bail only behind the next barrier, when every wavefront has read it
 	uint32_t fixed_ok;                  // the tables in lit / dist are the fixed code's (they stand from stream to stream)
 	uint32_t span_m, span_len, span_dist;   // the match that reaches from the first half of the output into the second
 	uint32_t prof[P_N], tprev[2], tripmax;
@@ -697,8 +698,9 @@ NXZ_WG_PHASE void read_lengths(uint32_t T)
 		if (L.bail) return;
 		if (L.hstate == 1) break;
 	}
-	if (tid == 0) { if (L.hend > T) L.bail = R_DHT; else L.pos = L.hend; }
+	// (behind a barrier: a wavefront may still be reading L.bail at the loop's end, and L.pos and L.bail are read behind the caller's barrier)
 	__syncthreads();
+	if (tid == 0) { if (L.hend > T) L.bail = R_DHT; else L.pos = L.hend; }
 }
 
 // ---- the decode tables of a block from L.lens (all lanes; R_TABLES in L.bail: the sub-tables do not fit) ----
@@ -1107,6 +1109,7 @@ __device__ __forceinline__ void inflate_wg_body(const nxz_batch_job_t *__restric
 						} else if (L.btype == 3) L.bail = R_HEADER;
 						L.pos = p;
 						L.inblock = L.btype == 0 ? 2 : 1;
+						L.hbad = 0;
 					}
 				}
 				__syncthreads();
@@ -1118,12 +1121,14 @@ __device__ __forceinline__ void inflate_wg_body(const nxz_batch_job_t *__restric
 				if (btype != 0 && !(btype == 1 && L.fixed_ok)) {
 					// ---- code lengths ----
 					if (btype == 2) {
+						// (wavefront 0's verdict goes to L.hbad and becomes L.bail behind the barriers below: the other wavefronts may still
+						// be reading L.bail behind the barrier above, and one that saw the reason there would leave the others at theirs)
 						if (wave == 0) {
 							const bool ok = read_header(L.pos, T, lane, true);
-							if (!ok && lane == 0) L.bail = R_DHT;
+							if (!ok && lane == 0) L.hbad = 1;
 						}
 						__syncthreads();
-						if (!L.bail) read_lengths(T);
+						if (!L.hbad) read_lengths(T);
 					} else {
 						for (int i = tid; i < 320; i += NT) L.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
 						if (tid == 0) { L.hlit = 288; L.hdist = 30; }
@@ -1132,16 +1137,16 @@ __device__ __forceinline__ void inflate_wg_body(const nxz_batch_job_t *__restric
 					if (L.bail) continue;
 					const int hlit = (int)L.hlit, hdist = (int)L.hdist;
 					// (the checks of nxzi::read_dht: an end-of-block code, no code over-subscribed)
-					if (btype == 2 && wave == 0) {
+					if (btype == 2 && wave == 0 && !L.hbad) {
 						uint32_t k1 = 0, k2 = 0;
 						for (int i = lane; i < hlit; i += 64) if (L.lens[i]) k1 += 1u << (15 - L.lens[i]);
 						if (lane < hdist && L.lens[hlit + lane]) k2 = 1u << (15 - L.lens[hlit + lane]);
 						k1 = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(k1, lane), 63);
 						k2 = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_incl(k2, lane), 63);
-						if (lane == 0 && (L.lens[256] == 0 || k1 > (1u << 15) || k2 > (1u << 15))) L.bail = R_DHT;
+						if (lane == 0 && (L.lens[256] == 0 || k1 > (1u << 15) || k2 > (1u << 15))) L.hbad = 1;   // (not L.bail: see above)
 					}
 					__syncthreads();
-					if (L.bail) continue;
+					if (L.hbad) { if (tid == 0) L.bail = R_DHT; continue; }
 					if (PROF) { WGPROF(P_DHT); if (tid == 0) L.prof[P_BLOCKS]++; }
 					if (tid == 0) L.fixed_ok = 0;
 					build_tables(hlit, hdist);

@@ -4,6 +4,11 @@
 // stream; every stream it does not take is on the hand-back list (and only those); damaged streams are handed back, never
 // "decoded".
 //   usage: inflate_wg_sim <file with sample text> [seed] [pmin_bits] [pieces a wavefront walks] [bytes of the long cases]
+//          inflate_wg_sim --cases <case file> <result file> [pmin_bits] [pieces a wavefront walks]
+// The second form judges nothing: it runs the streams of a file somebody else wrote (tests/test_inflate_wg_sim.py: the
+// hand-built streams of tests/deflate_handmade.py) as one launch and writes what the kernel left, for the caller to compare.
+//   case file:   u32 n, then n times { u32 src_len, hist_len, dst_cap, offset of src in its 16-byte granule; src_len bytes }
+//   result file: n times { u32 handed back, cc, tpbc, sfbt, subc, spbc, bytes behind dst_cap still as they were; tpbc bytes (taken only) }
 #include "hip_cpu_shim.h"
 #include "../../power-gzip_amd/csrc/nxz_inflate_wg.hip"
 #include <zlib.h>
@@ -30,8 +35,54 @@ static std::vector<uint8_t> deflate_raw(const std::vector<uint8_t> &in, int leve
 
 struct Case { std::string name; std::vector<uint8_t> plain, stream; bool expect_taken; uint32_t src_off; uint32_t cap; };
 
+static int run_case_file(const char *in, const char *outp, uint32_t pmin, uint32_t nres)
+{
+	FILE *f = fopen(in, "rb");
+	if (!f) { perror(in); return 2; }
+	uint32_t n = 0;
+	if (fread(&n, 4, 1, f) != 1 || n > 4096) { fprintf(stderr, "%s: no case file\n", in); return 2; }
+	const uint32_t GUARD = 64;
+	std::vector<nxz_batch_job_t> jobs(n);
+	std::vector<nxz_batch_result_t> res(n);
+	std::vector<std::vector<uint8_t>> srcbuf(n), dstbuf(n);
+	for (uint32_t i = 0; i < n; i++) {
+		uint32_t h[4];
+		if (fread(h, 4, 4, f) != 4 || h[0] > (1u << 24) || h[2] > (1u << 24) || h[3] > 15) { fprintf(stderr, "%s: case %u\n", in, i); return 2; }
+		srcbuf[i].assign(h[0] + 64 + 32, 0xa5);
+		uint8_t *base = (uint8_t *)(((uintptr_t)srcbuf[i].data() + 15) & ~(uintptr_t)15) + h[3];
+		if (h[0] && fread(base, 1, h[0], f) != h[0]) { fprintf(stderr, "%s: case %u is cut short\n", in, i); return 2; }
+		dstbuf[i].assign(h[2] + GUARD + 32, 0xaa);
+		memset(&jobs[i], 0, sizeof(jobs[i]));
+		jobs[i].src = base; jobs[i].dst = (uint8_t *)(((uintptr_t)dstbuf[i].data() + 15) & ~(uintptr_t)15);
+		jobs[i].src_len = h[0]; jobs[i].hist_len = h[1]; jobs[i].dst_cap = h[2]; jobs[i].in_adler = 1;
+		memset(&res[i], 0xff, sizeof(res[i]));
+	}
+	fclose(f);
+	std::vector<uint32_t> bail(64 + n, 0), dbg(16, 0);
+	uint32_t ctr = 0;
+	hipsim_run_block(0, 1, nxzw::NT, [&] { nxzw::inflate_wg_kernel<false>(jobs.data(), n, res.data(), nullptr, &ctr, bail.data(), pmin | 1024u << 16, nres, dbg.data(), nullptr); });
+	std::vector<bool> handed(n, false);
+	for (uint32_t k = 0; k < bail[0]; k++) handed[bail[64 + k]] = true;
+	FILE *o = fopen(outp, "wb");
+	if (!o) { perror(outp); return 2; }
+	for (uint32_t i = 0; i < n; i++) {
+		const uint8_t *dst = jobs[i].dst;
+		uint32_t intact = 1;
+		for (uint32_t k = 0; k < GUARD; k++) if (dst[jobs[i].dst_cap + k] != 0xaa) intact = 0;
+		const uint32_t rec[7] = { handed[i] ? 1u : 0u, res[i].cc, res[i].tpbc, res[i].sfbt, res[i].subc, res[i].spbc, intact };
+		fwrite(rec, 4, 7, o);
+		if (!handed[i] && res[i].tpbc <= jobs[i].dst_cap) fwrite(dst, 1, res[i].tpbc, o);
+	}
+	fclose(o);
+	printf("%u streams, %u handed back, reasons:", n, bail[0]);
+	for (int r = 1; r < 12; r++) printf(" %u", dbg[r]);
+	printf("\nran\n");
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc >= 4 && !strcmp(argv[1], "--cases")) return run_case_file(argv[2], argv[3], argc > 4 ? (uint32_t)atoi(argv[4]) : 128, argc > 5 ? (uint32_t)atoi(argv[5]) : 16);
 	if (argc < 2) { fprintf(stderr, "usage: %s <text file> [seed] [pmin_bits]\n", argv[0]); return 2; }
 	std::vector<uint8_t> text;
 	{

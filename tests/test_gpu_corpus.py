@@ -5,8 +5,12 @@ tests/corpus.py) through the engine, called through the C ABI.
 
   * COMPRESS_DHTGEN (LZ77 kernel -> device dhtgen -> entropy kernel): bytes == the oracle's, zlib inflates
     every block, compressed size per class >= 0.95 x zlib -1 on the identical chunks (the target's floor);
-  * the same chunks as zlib -6 raw streams through all three inflate kernels: bytes == source, CRC == zlib's.
+  * the same chunks as zlib -6 raw streams through the inflate routes a batch of this kind can take -- a stream per
+    workgroup (the engine's default and what the benchmark measures: no stream handed back), per lane, per wavefront
+    with its window in LDS or in the target -- and once with no knob set, by the engine's own routing: bytes == source,
+    CRC == zlib's.
 """
+import contextlib
 import ctypes as C
 import importlib
 import os
@@ -17,6 +21,7 @@ import pytest
 
 import corpus
 import oracle_lib as O
+from inflate_routes import inflate_route
 
 pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("power-gzip_amd")
@@ -83,41 +88,55 @@ def test_every_corpus_block_dhtgen_equals_oracle_and_keeps_the_ratio_floor(eng, 
     assert sum(v[1] for v in per.values()) / sum(v[0] for v in per.values()) >= 0.97
 
 
-@pytest.mark.parametrize("kernel", ["lanes", "waves", "waves-global-window"])
+KNOBS = ("NXZ_INFLATE_LANES_MIN", "NXZ_INFLATE_CUT", "NXZ_INFLATE_CUT_PIECES", "NXZ_INFLATE_WG", "NXZ_INFLATE_WG_MAX", "NXZ_WG_PMIN", "NXZ_WG_COOP",
+         "NXZ_INFLATE_ORDER", "NXZ_INFLATE_LDS_MAX", "NXZ_LANES_FIXED")
+
+
+@contextlib.contextmanager
+def no_knobs():
+    """none of the inflate knobs in the environment (the engine's own routing), and afterwards the environment as it was"""
+    old = {k: os.environ.pop(k, None) for k in KNOBS}
+    try:
+        yield None
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+@pytest.mark.parametrize("kernel", ["lanes", "waves", "waves-global-window", "wg", "engine-routing"])
 def test_every_corpus_block_as_a_zlib6_stream_inflates_on_every_kernel(blocks, kernel):
     import torch
-    old = {k: os.environ.get(k) for k in ("NXZ_INFLATE_LANES_MIN", "NXZ_INFLATE_LDS_MAX")}
-    os.environ["NXZ_INFLATE_LANES_MIN"] = "32" if kernel == "lanes" else "1000000000"
-    if kernel == "waves-global-window":
-        os.environ["NXZ_INFLATE_LDS_MAX"] = "0"
-    e = pkg.Engine(0)
-    try:
-        _, bl = blocks
-        raw = [b for _, _, b in bl]
-        streams = []
-        for b in raw:
-            c = zlib.compressobj(6, zlib.DEFLATED, -15)
-            streams.append(c.compress(b) + c.flush())
-        cstride = (max(len(s) for s in streams) + 64 + 15) & ~15
-        host = np.zeros((len(raw), cstride), np.uint8)
-        for i, s in enumerate(streams):
-            host[i, :len(s)] = np.frombuffer(s, np.uint8)
-        src = torch.from_numpy(host).to(e.dev)
-        dst = torch.zeros((len(raw), BLOCK), dtype=torch.uint8, device=e.dev)
-        jobs = e.jobs_strided(src, cstride, np.array([len(s) for s in streams], np.uint32), dst, BLOCK, BLOCK)
-        r = e.results_to_host(e.decompress(jobs, len(raw)))
-        got = dst.cpu().numpy()
-        for i, (cls, fname, b) in enumerate(bl):
-            assert r["cc"][i] == 0 and r["tpbc"][i] == len(b), (kernel, i, cls, fname, r["cc"][i])
-            assert got[i, :len(b)].tobytes() == b, (kernel, i, cls, fname)
-            assert r["crc"][i] == zlib.crc32(b) and r["adler"][i] == zlib.adler32(b), (kernel, i, cls, fname)
-    finally:
-        e.close()
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    with no_knobs(), (contextlib.nullcontext() if kernel == "engine-routing" else inflate_route(kernel)):
+        e = pkg.Engine(0)
+        try:
+            _, bl = blocks
+            raw = [b for _, _, b in bl]
+            streams = []
+            for b in raw:
+                c = zlib.compressobj(6, zlib.DEFLATED, -15)
+                streams.append(c.compress(b) + c.flush())
+            cstride = (max(len(s) for s in streams) + 64 + 15) & ~15
+            host = np.zeros((len(raw), cstride), np.uint8)
+            for i, s in enumerate(streams):
+                host[i, :len(s)] = np.frombuffer(s, np.uint8)
+            src = torch.from_numpy(host).to(e.dev)
+            dst = torch.zeros((len(raw), BLOCK), dtype=torch.uint8, device=e.dev)
+            jobs = e.jobs_strided(src, cstride, np.array([len(s) for s in streams], np.uint32), dst, BLOCK, BLOCK)
+            r = e.results_to_host(e.decompress(jobs, len(raw)))
+            got = dst.cpu().numpy()
+            for i, (cls, fname, b) in enumerate(bl):
+                assert r["cc"][i] == 0 and r["tpbc"][i] == len(b), (kernel, i, cls, fname, r["cc"][i])
+                assert got[i, :len(b)].tobytes() == b, (kernel, i, cls, fname)
+                assert r["crc"][i] == zlib.crc32(b) and r["adler"][i] == zlib.adler32(b), (kernel, i, cls, fname)
+            if kernel == "wg":
+                why = e.wg_reasons()
+                assert why is not None and why["handed_back"] == 0, why
+            if kernel == "engine-routing":                # (this engine's only batch: it went a stream per workgroup, the default route)
+                assert e.wg_reasons() is not None
+        finally:
+            e.close()
 
 
 def test_c5_mixed_batch_round_trip():

@@ -15,6 +15,7 @@ import pytest
 import framing as F
 import oracle_lib as O
 from datagen import make_block
+from deflate_handmade import fib_table, hand_table
 
 pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("power-gzip_amd")
@@ -153,52 +154,6 @@ def test_source_lengths_and_alignments(eng):
     r = size(eng, bufs, offs=offs)
     for i, b in enumerate(bufs):
         check_against_oracle(r, i, b, 30000)
-
-
-def fib_table():
-    """a dynamic table with literal/length codes of up to 15 bits and distance codes beyond 9 (more than the kernels' fast tables
-    index: LBITS = 11, DBITS = 9): Fibonacci-like counts make the deepest Huffman trees"""
-    ll = (C.c_uint32 * 286)(*([1] * 286))
-    dd = (C.c_uint32 * 30)(*([1] * 30))
-    a, b = 1, 2
-    for k in range(24):
-        ll[97 + k] = b
-        a, b = b, a + b
-    a, b = 1, 2
-    for k in range(20):
-        dd[29 - k] = b                                  # the SHORT distances keep the long codes
-        a, b = b, a + b
-    dht, dhtlen = O.dhtgen(ll, dd)
-    codes = O.Codes()
-    assert O.lib().nxo_dht_parse(dht, dhtlen, C.byref(codes)) == dhtlen
-    return dht, dhtlen, codes
-
-
-def hand_table():
-    """a complete code written by hand in which both alphabets reach 15 bits (O.dhtgen stops at 14 and 12 on any counts): every
-    symbol has a code, bytes 200..206 and the distances 1..12 have those of 10 to 15 bits.  Returns (bit string, bits)."""
-    ll = [9] * 286
-    for sym, n in ((101, 2), (32, 3), (116, 4), (97, 7), (111, 8), (110, 8)):       # Kraft sum 1 with 280 codes of 9 bits
-        ll[sym] = n
-    L = 9
-    for k in range(6):                                     # {L, 9, 9} -> {L + 1, 8, L + 1}: the sum stays, the longest code grows
-        ll[206], ll[120 + k], ll[200 + k] = L + 1, 8, L + 1
-        L += 1
-    chain = [4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 15]
-    dd = chain[::-1] + [2, 3, 4] + [5] * 14                # distance symbols 0..6 (distances 1..12): 15, 15, 14, 13, 12, 11, 10 bits
-    assert len(ll) == 286 and len(dd) == 30
-    v, n = 0, 0
-
-    def put(val, nbits):
-        nonlocal v, n
-        v |= val << n
-        n += nbits
-    put(29, 5); put(29, 5); put(15, 4)                      # HLIT, HDIST, HCLEN = 19
-    for sym in (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15):
-        put(4 if sym < 16 else 0, 3)                       # the code-length code: sixteen codes of 4 bits, symbol k = code k
-    for x in ll + dd:
-        put(int(format(x, "04b")[::-1], 2), 4)
-    return v.to_bytes((n + 7) // 8, "little"), n
 
 
 def kraft(lens):
