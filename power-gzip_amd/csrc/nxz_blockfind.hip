@@ -380,8 +380,9 @@ __global__ __launch_bounds__(NT) void find_blocks_kernel(const uint8_t *__restri
 			const uint32_t kc = atomicAdd(&ncand, 1u);
 			if (kc < MAXCAND) cand[kc] = p;
 		}
+		// (nq and the queue are used again by the next chunk)
+		__syncthreads();
 	}
-	__syncthreads();
 	if (diag == 1 || diag == 2) { if (t == 0) first[seg] = ~0ull - ncand; return; }          // (timing of phase 1 alone: tools)
 	// phase 2: the whole header, a lane per survivor.  Measured on 256 MiB of the corpus at zlib -6 (8 KiB segments): 55
 	// survivors a segment, and chance bits do NOT contradict themselves soon -- 42 of the 55 are still alive after 4

@@ -135,4 +135,17 @@ static inline void hipsim_run_block(unsigned b, unsigned nblocks, unsigned threa
 	pthread_barrier_destroy(&block_bar);
 	for (unsigned w = 0; w < threads / WAVE; w++) pthread_barrier_destroy(&wave_bar[w]);
 }
+// ---- what power-gzip_amd/csrc/nxz_blockfind.hip needs on top (tests/native/blockfind_sim.cpp; the file includes
+// <hip/hip_runtime.h> itself: tests/native/hip_sim/hip/hip_runtime.h stands in for it and includes this) ----
+struct __attribute__((aligned(8))) uint2 { uint32_t x, y; };
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{ x, y, z, w }; }
+static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{ x, y }; }
+struct dim3 { unsigned x, y, z; dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) { } };
+typedef struct hipsim_stream *hipStream_t;
+typedef int hipError_t;
+constexpr hipError_t hipSuccess = 0;
+static inline hipError_t hipGetLastError() { return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) { memset(p, v, n); return hipSuccess; }
+// the launchers of a kernel file compile and launch nothing: a simulation calls the kernels itself, a workgroup at a time
+#define hipLaunchKernelGGL(...) ((void)0)
 #endif
