@@ -826,6 +826,107 @@ int nxz_batch_deflate_streams_part(nxz_ctx_t *ctx, int fc, int fmt, int level, u
 				   nxz_stream_carry_t *carry /* DEVICE, n, in/out */,
 				   nxz_stream_result_t *results /* DEVICE, n */, void *stream);
 
+/* The decode side (additive): a batch of raw / zlib / gzip streams READ in parts, n streams a call, one part of each -- the pieces a
+ * socket, a range GET or nxz_batch_deflate_streams_part's own writer hand over.  jobs[] is a HOST array (it may be reused on
+ * return); carry[] and results[] are DEVICE arrays, read and written by the device only, so part k + 1 of the whole batch may be
+ * queued behind part k with no host step between.  fmt: NXZ_FMT_RAW (0), _ZLIB, _GZIP or _AUTO (per stream, as the framed call).
+ * A part is THIS call's compressed bytes (src, src_len: any alignment, any length, 0 included) and a target for THIS call's output
+ * (dst, dst_cap: any alignment; 16-byte aligned takes the faster route, as everywhere).  `prev` / prev_len: the OUTPUT bytes of
+ * the stream just in front of dst, of which the last min(32768, prev_len, total_out) count; prev + prev_len == dst is the ordinary
+ * case of outputs laid end to end.  The decode kernels want the history in front of the SOURCE, so the window is always staged:
+ * [window][tail][this part from the deflate data's first byte] goes into a 16-byte aligned slot of the stream's scratch (16 bytes
+ * a lane, sources of any alignment through aligned loads joined by a byte shift; one grid over all bytes of a chunk) and the raw
+ * batch decodes from there with NXZ_JOB_SUSPEND_WHEN_FULL.  A part with neither window nor tail is decoded where it lies.
+ * flags: NXZ_PART_FIRST only -- the incoming carry[i] is ignored and started afresh; there is no LAST, the stream says where it ends.
+ * carry[i] (fixed size, needs no initial value before a FIRST part) holds the phase (header / body / trailer / done / failed), the
+ * frame's facts and verdict so far (an nxz_batch_frame_t: offsets count from the stream's first byte, `end` = the bytes of the
+ * stream through its trailer), where the header's byte-wise state machine stands (which field, bytes left of FEXTRA or DICTID, the
+ * running header CRC for FHCRC: a header of any length may be cut anywhere, one byte a part included, and needs no tail), the decode
+ * state as nxz_stream_resume_t has it plus subc, crc / adler of all output, total_in / total_out / parts, and the TAIL: the
+ * tail_len source bytes that were handed over and must be seen again.  The stream stands at byte total_in - tail_len;
+ * [tail][next part] is its continuation and subc applies to the first byte of that.  A part that ends inside a token leaves at most
+ * 7 bytes there, one that ends inside a block header the header read so far (the engine suspends IN FRONT of a header it cannot
+ * finish), one that ends inside the trailer at most 7 bytes.
+ * results[i]: cc = the decode's own code (or NXZ_CC_INVALID_OP: refused); out_len = bytes written at dst by this part; crc / adler
+ * the running values of the whole stream; status and in_used:
+ *   NXZ_INFLATE_PART_MORE      the stream is open, send the next part; in_used = src_len
+ *   NXZ_INFLATE_PART_DONE      trailer read and checked; in_used = the byte behind it (bytes beyond are no error; a second gzip member
+ *                              is not decoded: start it with FIRST at src + in_used)
+ *   NXZ_INFLATE_PART_DST_FULL  suspended in front of the token that did not fit (a stored block: at the byte); in_used < src_len,
+ *                              0 when the target filled inside the old tail: send src + in_used again with a fresh target.  A target
+ *                              that fills at a token inside the part's last byte is MORE: that byte is the tail
+ *   NXZ_INFLATE_PART_FAILED    carry[i].frame.status says why (NXZ_FRAME_DEFLATE: look at cc); in_used = 0, behind a trailer that
+ *                              was read and does not match the byte behind it.  zlib FDICT: NXZ_FRAME_NEED_DICT with dictid set,
+ *                              nothing decoded
+ * Refused (cc = NXZ_CC_INVALID_OP, status FAILED; dst and carry[i] untouched, the neighbours unaffected, the part may be sent again):
+ * src == NULL with src_len != 0, dst == NULL with dst_cap != 0, prev == NULL with prev_len != 0, flag bits other than FIRST, FIRST
+ * with prev_len != 0, no FIRST on a carry that is done or failed.
+ * For a stream that arrives whole in one FIRST part dst, out_len, crc / adler, the frame's facts and in_used (= frame.end) are what
+ * nxz_batch_decompress_framed writes for the same bytes.
+ * The work goes chunk by chunk: NXZ_INFLATE_PART_SCRATCH (bytes, read at every call, default 512 MiB) bounds the staging slots of a
+ * chunk, a stream larger than it gets a chunk of its own, 16 384 streams a chunk at most; the result does not depend on it.  Per
+ * chunk: open (refusals, FIRST, header state machine, trailer, the derived job and its table slot), stage, nxz_batch_decompress kept
+ * off the stream-per-lane kernel as the fine range reads are (NXZ_JOB_SUSPEND_WHEN_FULL), close (result and table slot -> carry
+ * and results[i]).  Streams that are not in the body phase reach the decode as empty jobs.  On the device:
+ * power-gzip_amd/csrc/nxz_inflate_part.hip, the rules in nxz_inflate_part.h.
+ * NXZ_INFLATE_PART_TAIL: the longest dynamic block header RFC 1951 allows is 3 + 14 + 19 * 3 + 316 * 7 = 2286 bits (BFINAL / BTYPE;
+ * HLIT, HDIST, HCLEN; 19 code length code lengths; 316 lengths coded singly with 7-bit codes), it may start at any of the 8 bits of
+ * a byte: 2293 bits = 287 bytes, rounded up to the next multiple of 16 (tests/test_inflate_part_model_host.py builds that header).
+ * Asynchronous on `stream`: no host wait and no device allocation once the stream's scratch has grown.  Returns 0, -EINVAL (a NULL
+ * array with n > 0, an unknown fmt), -ENODEV, -E2BIG (n >= 2^31) or -ENOMEM as nxz_batch_deflate_streams_part does.
+ * Not part of this call: a shared dictionary; the gzip members that follow the first; size-only and verify-only forms; nx_inflate
+ * on top of it; zero-copy windows (a window that already lies in front of the source).
+ * Speed (tools/bench_inflate_part.py, profiles/r25_inflate_part.txt; 4096 zlib -6 streams of 1 MiB of output, medians of 5 runs taken in
+ * turn, every route within 0.4 % of its median but (r): 3 %): one FIRST part 1.063 of the time of nxz_batch_decompress_framed (52.57 against
+ * 49.45 ms; nothing is staged: the 3 ms are what the call puts around the same decode, not separated further).  A stream in 4 parts with all calls queued and one
+ * wait 268.0 ms, in 16 parts 199.7 ms: 5.4 and 4.0 times the framed call, and 0.73 and 0.28 of the only route there was before --
+ * nxz_batch_decompress with resume jobs, a host wait and host-built jobs and layouts between the parts: 367.1 and 701.5 ms.  The staging
+ * does not explain what the parts cost over the framed call: 1.33 and 3.05 GiB staged against 219 and 150 ms.  The time is the decode of
+ * the parts behind the first: a job with history or resume state goes a stream per wavefront, and a wavefront takes about 55 ms for a
+ * part of 256 KiB of output and 10 ms for one of 64 KiB however few streams there are -- 96 streams take 221 ms in 4 parts, queued or
+ * built by the host alike.  Resume jobs on the stream-per-workgroup kernel would take that away; that kernel is not part of this call. */
+#define NXZ_INFLATE_PART_TAIL 288
+enum { NXZ_INFLATE_PHASE_HEADER = 0, NXZ_INFLATE_PHASE_BODY, NXZ_INFLATE_PHASE_TRAILER, NXZ_INFLATE_PHASE_DONE, NXZ_INFLATE_PHASE_FAILED };
+enum { NXZ_INFLATE_PART_MORE = 0, NXZ_INFLATE_PART_DONE, NXZ_INFLATE_PART_DST_FULL, NXZ_INFLATE_PART_FAILED };
+typedef struct nxz_inflate_part_job {  /* HOST array, 40 bytes */
+	const uint8_t *src;            /* DEVICE, any alignment: this part's compressed bytes */
+	uint8_t       *dst;            /* DEVICE, any alignment: where THIS part's output goes */
+	const uint8_t *prev;           /* DEVICE or NULL, any alignment: the prev_len output bytes of the stream just in front of dst */
+	uint32_t       src_len;        /* any length, 0 included */
+	uint32_t       dst_cap;
+	uint32_t       prev_len;       /* any value; only the tail counts (above) */
+	uint32_t       flags;          /* NXZ_PART_FIRST */
+} nxz_inflate_part_job_t;
+typedef struct nxz_inflate_carry {     /* DEVICE, 704 bytes, one per stream, read and written by the device */
+	uint32_t phase;                /* NXZ_INFLATE_PHASE_* */
+	uint32_t hpos;                 /* header: the field the next byte belongs to (nxz_inflate_part.h) */
+	uint32_t hleft;                /* header: bytes left of FEXTRA / DICTID */
+	uint32_t hcrc;                 /* header: the CRC-32 register over the header bytes so far */
+	nxz_batch_frame_t frame;       /* the frame's facts and its verdict (status) so far */
+	uint32_t hfirst;               /* header: the stream's first byte (zlib CMF; NXZ_FMT_AUTO decides at the second) */
+	uint32_t sfbt, rem, dhtlen;    /* the decode state, as nxz_stream_resume_t */
+	uint32_t subc;                 /* unused bits of the first byte of [tail][next part], 0 = all eight */
+	uint32_t crc, adler;           /* of all output so far, from 0 / 1 */
+	uint32_t parts;                /* parts taken, empty ones included */
+	uint32_t tail_len;
+	uint32_t reserved[2];
+	uint64_t total_in, total_out;  /* source bytes taken / output bytes written so far */
+	uint8_t  dht[NXZ_DHT_MAXSZ];
+	uint8_t  tail[NXZ_INFLATE_PART_TAIL];
+} nxz_inflate_carry_t;
+typedef struct nxz_inflate_part_result { /* DEVICE, 32 bytes, written by the device */
+	uint32_t cc;
+	uint32_t status;               /* NXZ_INFLATE_PART_* */
+	uint32_t in_used;
+	uint32_t out_len;
+	uint32_t crc, adler;
+	uint32_t reserved[2];
+} nxz_inflate_part_result_t;
+int nxz_batch_inflate_streams_part(nxz_ctx_t *ctx, int fmt /* NXZ_FMT_RAW, ZLIB, GZIP, AUTO */,
+				   const nxz_inflate_part_job_t *jobs /* HOST */, size_t n,
+				   nxz_inflate_carry_t *carry /* DEVICE, n, in/out */,
+				   nxz_inflate_part_result_t *results /* DEVICE, n */, void *stream);
+
 /* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */

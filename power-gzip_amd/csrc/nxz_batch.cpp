@@ -2,6 +2,7 @@
 // kernels they get, their dictionary forms, table generation, wrap and the pack forms, nxz_trim, stage timing and the diagnostics.
 // (The calls around them -- framed streams, sizes, members, one-stream deflate, BGZF and checkpoints -- are nxz_batch_framed.cpp's.)
 #include "nxz_ctx.h"
+#include "nxz_inflate_part.h"
 
 // ---------------------------------------------------------------------------
 // batched, device-resident interface
@@ -43,6 +44,7 @@ static constexpr unsigned JOB_COUNTERS = 256;
 // 2.9) go through the wave kernel at 73 GiB/s from 32 768 streams on and through the lane kernel at 51 / 88 / 164 at 32 768 /
 // 65 536 / 262 144: the switch-over lies between the two kinds' break-evens.
 #define NXZ_LANES_MIN 49152
+static_assert(NXZ_INFLATE_PART_CHUNK_STREAMS < NXZ_LANES_MIN, "a chunk of nxz_batch_inflate_streams_part must stay below the batches that are sampled or go a stream per lane");
 #define NXZ_LANES_TABLES_MIN 163840   /* streams that bring tables: the lane kernel from here on */
 #define NXZ_WINDOW_LDS_MAX 1024
 #define NXZ_DICT_WG_MIN_DEFAULT 4096    /* nxz_batch_decompress_dict: source bytes from which a stream goes a workgroup each (profiles/r08_dict.txt: the two routes break even at about 4 KiB of source, 10 KiB of output) */

@@ -1,11 +1,12 @@
 // nxz_batch_framed.cpp -- the calls of include/nxz_engine.h's device-resident interface that put kernels of their own around a raw
 // batch (nxz_batch.cpp) or walk streams without decoding them: framed zlib / gzip streams, output sizes, multi-member gzip jobs,
-// one stream per device buffer, BGZF discovery, index and range reads, checkpoint index and range reads (one stream's, and a batch's).
+// one stream per device buffer (written, and read in parts), BGZF discovery, index and range reads, checkpoint index and range reads (one stream's, and a batch's).
 #include <functional>
 #include "nxz_ctx.h"
 #include "nxz_streams_dict.h"
 #include "nxz_streams_index.h"
 #include "nxz_streams_part.h"
+#include "nxz_inflate_part.h"
 #include "nxz_checkpoint_fine.h"
 #include "nxz_checkpoint_batch.h"
 
@@ -484,6 +485,90 @@ extern "C" int nxz_batch_deflate_streams_part(nxz_ctx_t *c, int fc, int fmt, int
 		i_lo = i_hi;
 	}
 	return launched("streams part epilogue launch", nxz_launch_streams_part_epilogue(d_desc, d_first, ns, hist_max, fmt, d_state, carry, results, s));
+}
+
+// ---------------------------------------------------------------------------
+// A stream READ in parts (nxz_inflate_part.hip, the rules in nxz_inflate_part.h): per chunk open -> stage -> the raw batch on the
+// derived jobs with their table slots as dht_io -> close, everything on `s` and no host wait; the same pinned staging and upload,
+// BUF_STREAMS under frame_use[s].  What the host cannot see is the carry -- the phase, the window that counts, the tail --, so its
+// one pass sets aside the most a part's slot can take (nxz_inflate_part_slot_bound) and cuts the batch into chunks by that: a chunk
+// ends in front of the stream that would carry its slots beyond NXZ_INFLATE_PART_SCRATCH bytes (a stream larger than that is a
+// chunk of its own) or at NXZ_INFLATE_PART_CHUNK_STREAMS streams.  off[] goes up beside the descriptors: a chunk of m streams has
+// m + 1 entries, the first 0, the last its staging bytes.  The decode is kept off the stream-per-lane kernel as the fine range reads
+// are (fine_chunk_route below): the jobs bring NXZ_JOB_SUSPEND_WHEN_FULL.
+// ---------------------------------------------------------------------------
+static int fine_chunk_route();
+
+static uint64_t inflate_part_scratch()
+{
+	const char *e = getenv("NXZ_INFLATE_PART_SCRATCH");                 // (read at every call: the tests switch it)
+	const uint64_t v = e ? strtoull(e, nullptr, 0) : 0;
+	return v ? v : NXZ_INFLATE_PART_SCRATCH_DEFAULT;
+}
+
+extern "C" int nxz_batch_inflate_streams_part(nxz_ctx_t *c, int fmt, const nxz_inflate_part_job_t *jobs, size_t n, nxz_inflate_carry_t *carry,
+					      nxz_inflate_part_result_t *results, void *stream)
+{
+	if (!c || !nxz_inflate_part_fmt_ok(fmt) || (n && (!jobs || !results || !carry))) return -EINVAL;
+	if (forked_child()) return -ENODEV;
+	if (!n) return 0;
+	if (n >= (1u << 31)) return -E2BIG;
+	for (size_t i = 0; i < n; i++)
+		if (nxz_inflate_part_slot_bound(&jobs[i]) > 0xffffffffull) return -E2BIG;   // (window + tail + part is a raw job's src_len)
+	(void)hipSetDevice(c->device);
+	hipStream_t s = (hipStream_t)stream;
+	std::lock_guard<std::mutex> use(*frame_mutex(c, s));
+	const uint64_t scratch = inflate_part_scratch();
+	auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+	// what is uploaded: [descriptors][off], the same layout in the staging and in the device buffer (a chunk a stream at the worst: 2 n entries)
+	const size_t o_off = up(n * sizeof(nxz_inflate_part_job_t)), up_bytes = o_off + 2 * n * sizeof(uint64_t);
+	uint8_t *st_h = nullptr;
+	hipEvent_t st_ev = nullptr;
+	int rc = streams_staging(c, s, up_bytes, &st_h, &st_ev);
+	if (rc) return rc;
+	// one pass over the streams: the chunks and the slots' offsets inside them
+	uint64_t *const h_off = (uint64_t *)(st_h + o_off);
+	memcpy(st_h, jobs, n * sizeof(nxz_inflate_part_job_t));
+	uint64_t cur = 0, max_bytes = 0;
+	size_t e = 0;
+	uint32_t cnt = 0, max_cnt = 0;
+	for (size_t i = 0; i < n; i++) {
+		const uint64_t b = nxz_inflate_part_slot_bound(&jobs[i]);
+		if (cnt && (cur + b > scratch || cnt == NXZ_INFLATE_PART_CHUNK_STREAMS)) { h_off[e++] = cur; cur = 0; cnt = 0; }
+		h_off[e++] = cur;
+		cur += b; cnt++;
+		max_bytes = std::max(max_bytes, cur); max_cnt = std::max(max_cnt, cnt);
+	}
+	h_off[e++] = cur;
+	const size_t C = max_cnt;
+	const size_t o_work = up(up_bytes), o_jobs = o_work + up(C * sizeof(nxz_inflate_part_work_t)), o_res = o_jobs + up(C * sizeof(nxz_batch_job_t)),
+		     o_dht = o_res + up(C * sizeof(nxz_batch_result_t)), o_stage = o_dht + up(C * sizeof(nxz_batch_dht_t)), d_bytes = o_stage + (size_t)max_bytes;
+	uint8_t *const d = with_scratch(c, s, [&](nxz_ctx::Scratch &r) {
+		(void)r.buf[BUF_STREAMS].grow(s, d_bytes);
+		return r.buf[BUF_STREAMS].p;
+	});
+	if (!d) return -ENOMEM;
+	const nxz_inflate_part_job_t *const d_desc = (const nxz_inflate_part_job_t *)d;
+	const uint64_t *const d_off = (const uint64_t *)(d + o_off);
+	nxz_inflate_part_work_t *const d_work = (nxz_inflate_part_work_t *)(d + o_work);
+	nxz_batch_job_t *const d_jobs = (nxz_batch_job_t *)(d + o_jobs);
+	nxz_batch_result_t *const d_res = (nxz_batch_result_t *)(d + o_res);
+	nxz_batch_dht_t *const d_dht = (nxz_batch_dht_t *)(d + o_dht);
+	uint8_t *const d_stage = d + o_stage;
+	if ((rc = streams_upload(c, s, d, st_h, up_bytes, st_ev)) != 0) return rc;
+	size_t e0 = 0;
+	for (size_t i0 = 0; i0 < n;) {
+		uint32_t m = 1;                                                  // the chunk's entries end in front of the next chunk's 0
+		while (e0 + m + 1 < e && h_off[e0 + m + 1] != 0) m++;
+		rc = nxz_launch_inflate_part_open(d_desc + i0, m, fmt, carry + i0, d_off + e0, d_stage, d_jobs, d_dht, d_work, results + i0, s);
+		if (!rc) rc = nxz_launch_inflate_part_stage(d_desc + i0, carry + i0, d_off + e0, m, h_off[e0 + m], d_work, d_jobs, s);
+		if ((rc = launched("inflate part stage launch", rc)) != 0) return rc;
+		if ((rc = batch_decompress(c, d_jobs, m, d_res, d_dht, s, fine_chunk_route())) != 0) return rc;
+		if ((rc = launched("inflate part close launch", nxz_launch_inflate_part_close(d_desc + i0, m, carry + i0, d_jobs, d_res, d_dht, d_work, results + i0, s))) != 0)
+			return rc;
+		i0 += m; e0 += m + 1;
+	}
+	return 0;
 }
 
 // The members of a BGZF image in device memory (nxz_launch_bgzf_discover; with coff: nxz_launch_bgzf_coff behind it), then

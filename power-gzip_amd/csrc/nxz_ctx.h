@@ -88,7 +88,7 @@ enum ScratchBuf {
 	BUF_RNG,            // nxz_bgzf_read_ranges: the map's per-range and per-member arrays
 	BUF_RNG_SLOTS,      // ... a chunk of decoded members (16-byte aligned slots), their jobs, frames and results
 	BUF_RNG_BATCH,      // nxz_batch_checkpoint_read_ranges: the rows' verdicts and bases, the flat uoff, the ranges mapped onto it
-	BUF_STREAMS,        // nxz_batch_deflate_streams: descriptors, block prefix and state of the streams; jobs, results, owners, offsets and output slots of a chunk
+	BUF_STREAMS,        // nxz_batch_deflate_streams: descriptors, block prefix and state of the streams; jobs, results, owners, offsets and output slots of a chunk; nxz_batch_inflate_streams_part: descriptors and slot offsets; work, jobs, results, table slots and staging slots of a chunk
 	BUF_GZIP_MEMBERS,   // nxz_batch_gzip_members_decode: the per-job plan, and the members as framed jobs with their owners, frames and results
 	BUF_COUNT
 };

@@ -275,6 +275,19 @@ int nxz_launch_streams_part_pack(const nxz_stream_part_job_t *desc, const uint32
 				 const nxz_stream_state_t *state, hipStream_t stream);
 int nxz_launch_streams_part_epilogue(const nxz_stream_part_job_t *desc, const uint32_t *first, uint32_t n, uint32_t hist_max, int fmt,
 				     const nxz_stream_state_t *state, nxz_stream_carry_t *carry, nxz_stream_result_t *results, hipStream_t stream);
+/* nxz_inflate_part.hip: a stream read in parts, a device buffer a part (nxz_batch_inflate_streams_part; nxz_inflate_part.h has the rules).
+ * The kernels around the raw decode of a chunk of m streams: desc, carry and results are the chunk's; off[m + 1]: where each stream's
+ * slot begins in `stage`; work: what open tells stage and close about a stream (the offset of the deflate data's first byte in the
+ * part, whether it goes through the decode, whether it is staged); jobs, dres and dht: the raw batch's jobs, results and dht_io */
+typedef struct nxz_inflate_part_work { uint32_t body, live, staged, reserved; } nxz_inflate_part_work_t;
+int nxz_launch_inflate_part_open(const nxz_inflate_part_job_t *desc, uint32_t m, int fmt, nxz_inflate_carry_t *carry, const uint64_t *off,
+				 uint8_t *stage, nxz_batch_job_t *jobs, nxz_batch_dht_t *dht, nxz_inflate_part_work_t *work,
+				 nxz_inflate_part_result_t *results, hipStream_t stream);
+int nxz_launch_inflate_part_stage(const nxz_inflate_part_job_t *desc, const nxz_inflate_carry_t *carry, const uint64_t *off, uint32_t m,
+				  uint64_t bytes, const nxz_inflate_part_work_t *work, const nxz_batch_job_t *jobs, hipStream_t stream);
+int nxz_launch_inflate_part_close(const nxz_inflate_part_job_t *desc, uint32_t m, nxz_inflate_carry_t *carry, const nxz_batch_job_t *jobs,
+				  const nxz_batch_result_t *dres, const nxz_batch_dht_t *dht, const nxz_inflate_part_work_t *work,
+				  nxz_inflate_part_result_t *results, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

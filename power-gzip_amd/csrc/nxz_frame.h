@@ -26,13 +26,17 @@ NXZ_HD inline uint32_t nxz_rd32be(const uint8_t *p) { return (uint32_t)p[0] << 2
 
 // ---- CRC-32 (reflected, polynomial 0xedb88320) in pieces --------------------------------------------------------
 // the register over n bytes from 0, without the initial and final inversion
+// ... one byte more
+NXZ_HD inline uint32_t nxz_crc_step(uint32_t c, uint32_t byte)
+{
+	c ^= byte;
+	for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1) ? 0xedb88320u : 0);
+	return c;
+}
 NXZ_HD inline uint32_t nxz_crc_raw(const uint8_t *p, uint32_t n)
 {
 	uint32_t c = 0;
-	for (uint32_t i = 0; i < n; i++) {
-		c ^= p[i];
-		for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1) ? 0xedb88320u : 0);
-	}
+	for (uint32_t i = 0; i < n; i++) c = nxz_crc_step(c, p[i]);
 	return c;
 }
 // a * b mod P in the reflected representation (0x80000000 = 1)
@@ -69,13 +73,31 @@ NXZ_HD inline uint32_t nxz_crc_part(const uint8_t *p, uint32_t lo, uint32_t hi, 
 NXZ_HD inline uint32_t nxz_crc_finish(uint32_t parts, uint32_t n) { return ~(parts ^ nxz_gf_mul(0xffffffffu, nxz_x8n(n))); }
 
 // ---- the header --------------------------------------------------------------------------------------------------
+// The field rules, one copy for the parser below and for the byte-wise state machine of a stream read in parts (nxz_inflate_part.h).
+// zlib's two bytes, in zlib's order of checks: NXZ_FRAME_OK, _BAD_HEADER (FCHECK, CINFO > 7), _BAD_METHOD or _NEED_DICT (FDICT)
+NXZ_HD inline uint32_t nxz_zlib_header_status(uint32_t cmf, uint32_t flg)
+{
+	if ((cmf * 256 + flg) % 31) return NXZ_FRAME_BAD_HEADER;
+	if ((cmf & 15) != 8) return NXZ_FRAME_BAD_METHOD;
+	if ((cmf >> 4) > 7) return NXZ_FRAME_BAD_HEADER;
+	return flg & 0x20 ? NXZ_FRAME_NEED_DICT : NXZ_FRAME_OK;
+}
+// byte i (0 .. 3) of a gzip header: ID1, ID2, CM, FLG
+NXZ_HD inline uint32_t nxz_gzip_fixed_status(uint32_t i, uint32_t byte)
+{
+	return i == 0 ? (byte != 0x1f ? NXZ_FRAME_BAD_HEADER : NXZ_FRAME_OK) : i == 1 ? (byte != 0x8b ? NXZ_FRAME_BAD_HEADER : NXZ_FRAME_OK)
+	     : i == 2 ? (byte != 8 ? NXZ_FRAME_BAD_METHOD : NXZ_FRAME_OK) : ((byte & 0xe0) ? NXZ_FRAME_BAD_HEADER : NXZ_FRAME_OK);
+}
+// is this the gzip magic? (NXZ_FMT_AUTO)
+NXZ_HD inline bool nxz_gzip_magic(uint32_t b0, uint32_t b1) { return b0 == 0x1f && b1 == 0x8b; }
+
 // Fills f (status, format, hdr_len and the header's fields; end / check / isize are the trailer's, left 0) and
 // returns the status.  fmt: NXZ_FMT_ZLIB / _GZIP / _AUTO.
 template <class Ops>
 NXZ_HD inline uint32_t nxz_frame_parse(const uint8_t *p, uint32_t len, int fmt, nxz_batch_frame_t *f, Ops &ops)
 {
 	*f = nxz_batch_frame_t();
-	const bool gz = fmt == NXZ_FMT_GZIP || (fmt == NXZ_FMT_AUTO && len >= 2 && p[0] == 0x1f && p[1] == 0x8b);
+	const bool gz = fmt == NXZ_FMT_GZIP || (fmt == NXZ_FMT_AUTO && len >= 2 && nxz_gzip_magic(p[0], p[1]));
 	f->format = gz ? NXZ_FMT_GZIP : NXZ_FMT_ZLIB;
 	uint32_t st = NXZ_FRAME_OK;
 	if (!gz) {
@@ -83,26 +105,24 @@ NXZ_HD inline uint32_t nxz_frame_parse(const uint8_t *p, uint32_t len, int fmt, 
 		else {
 			const uint32_t cmf = p[0], flg = p[1];
 			f->flg = (uint8_t)flg; f->cinfo = (uint8_t)(cmf >> 4);
-			if ((cmf * 256 + flg) % 31) st = NXZ_FRAME_BAD_HEADER;
-			else if ((cmf & 15) != 8) st = NXZ_FRAME_BAD_METHOD;
-			else if ((cmf >> 4) > 7) st = NXZ_FRAME_BAD_HEADER;
-			else if (flg & 0x20) {
+			st = nxz_zlib_header_status(cmf, flg);
+			if (st == NXZ_FRAME_NEED_DICT) {
 				if (len < 6) st = NXZ_FRAME_TRUNCATED;
-				else { f->dictid = nxz_rd32be(p + 2); f->hdr_len = 6; st = NXZ_FRAME_NEED_DICT; }
-			} else f->hdr_len = 2;
+				else { f->dictid = nxz_rd32be(p + 2); f->hdr_len = 6; }
+			} else if (st == NXZ_FRAME_OK) f->hdr_len = 2;
 		}
 		f->status = st;
 		return st;
 	}
 	uint32_t q = 10;
 	if (len < 1) st = NXZ_FRAME_TRUNCATED;
-	else if (p[0] != 0x1f) st = NXZ_FRAME_BAD_HEADER;
+	else if ((st = nxz_gzip_fixed_status(0, p[0])) != NXZ_FRAME_OK) ;
 	else if (len < 2) st = NXZ_FRAME_TRUNCATED;
-	else if (p[1] != 0x8b) st = NXZ_FRAME_BAD_HEADER;
+	else if ((st = nxz_gzip_fixed_status(1, p[1])) != NXZ_FRAME_OK) ;
 	else if (len < 3) st = NXZ_FRAME_TRUNCATED;
-	else if (p[2] != 8) st = NXZ_FRAME_BAD_METHOD;
+	else if ((st = nxz_gzip_fixed_status(2, p[2])) != NXZ_FRAME_OK) ;
 	else if (len < 4) st = NXZ_FRAME_TRUNCATED;
-	else if ((f->flg = p[3]) & 0xe0) st = NXZ_FRAME_BAD_HEADER;
+	else if ((st = nxz_gzip_fixed_status(3, f->flg = p[3])) != NXZ_FRAME_OK) ;
 	else if (len < 10) st = NXZ_FRAME_TRUNCATED;
 	else {
 		const uint32_t flg = p[3];
@@ -166,6 +186,17 @@ NXZ_HD inline uint32_t nxz_frame_trailer_bytes(uint32_t format) { return format 
 // from there a byte at a time.  Returns the status; *end, *check and *isize are the frame's fields, 0 unless the trailer was read.
 // compare_check: hold Adler-32 / CRC-32 against r's (the walk has none to compare: without it nothing is NXZ_FRAME_BAD_CHECK).
 // gzip's ISIZE is held against r->tpbc either way.
+// the trailer's bytes t against the output's checksums and length: *check and *isize as read, the verdict
+NXZ_HD inline uint32_t nxz_frame_trailer_status(uint32_t format, const uint8_t *t, uint32_t crc, uint32_t adler, uint32_t out_len, bool compare_check,
+						uint32_t *check, uint32_t *isize)
+{
+	if (format != NXZ_FMT_GZIP) {
+		*check = nxz_rd32be(t); *isize = 0;
+		return compare_check && *check != adler ? NXZ_FRAME_BAD_CHECK : NXZ_FRAME_OK;
+	}
+	*check = nxz_rd32le(t); *isize = nxz_rd32le(t + 4);
+	return compare_check && *check != crc ? NXZ_FRAME_BAD_CHECK : *isize != out_len ? NXZ_FRAME_BAD_LENGTH : NXZ_FRAME_OK;
+}
 NXZ_HD inline uint32_t nxz_frame_trailer(uint32_t format, uint32_t hdr_len, const nxz_batch_result_t *r, const uint8_t *src, uint32_t src_len,
 					 bool compare_check, uint32_t *end, uint32_t *check, uint32_t *isize)
 {
@@ -175,14 +206,8 @@ NXZ_HD inline uint32_t nxz_frame_trailer(uint32_t format, uint32_t hdr_len, cons
 	const uint32_t tl = nxz_frame_trailer_bytes(format);
 	const uint64_t dend = (uint64_t)hdr_len + r->spbc - (r->subc >> 3);
 	if (dend + tl > src_len) return NXZ_FRAME_TRUNCATED;
-	const uint8_t *t = src + dend;
 	*end = (uint32_t)dend + tl;
-	if (tl == 4) {
-		*check = nxz_rd32be(t);
-		return compare_check && *check != r->adler ? NXZ_FRAME_BAD_CHECK : NXZ_FRAME_OK;
-	}
-	*check = nxz_rd32le(t); *isize = nxz_rd32le(t + 4);
-	return compare_check && *check != r->crc ? NXZ_FRAME_BAD_CHECK : *isize != r->tpbc ? NXZ_FRAME_BAD_LENGTH : NXZ_FRAME_OK;
+	return nxz_frame_trailer_status(format, src + dend, r->crc, r->adler, r->tpbc, compare_check, check, isize);
 }
 
 // ---- BGZF: one member with the "BC" subfield at p (left bytes from there on) -------------------------------------

@@ -19,10 +19,12 @@
 #include <hip/hip_runtime.h>
 #include "nxz_streams_dev.h"
 #include "nxz_streams_part.h"
+#include "nxz_shift_load.h"
 
 namespace nxzsp {
 
 using nxzst::owner_of;
+using nxz::shift_bytes;
 
 __device__ inline nxz_stream_job_t plain_job(const nxz_stream_part_job_t &j)
 {
@@ -65,17 +67,6 @@ __global__ __launch_bounds__(256) void expand_kernel(const nxz_stream_part_job_t
 	}
 	jobs[t] = j;
 	owner[t] = i;
-}
-
-// out = the 16 bytes at byte `sh` (1 .. 15) of the 32 bytes [lo][hi]
-__device__ inline uint4 shift_bytes(const uint4 lo, const uint4 hi, uint32_t sh)
-{
-	uint64_t q0 = lo.x | (uint64_t)lo.y << 32, q1 = lo.z | (uint64_t)lo.w << 32, q2 = hi.x | (uint64_t)hi.y << 32;
-	const uint64_t q3 = hi.z | (uint64_t)hi.w << 32;
-	if (sh >= 8) { q0 = q1; q1 = q2; q2 = q3; sh -= 8; }
-	const uint32_t s = sh * 8;
-	const uint64_t a = s ? q0 >> s | q1 << (64 - s) : q0, b = s ? q1 >> s | q2 << (64 - s) : q1;
-	return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
 }
 
 // A workgroup of 256 per staged first block: slot <- [the last h0 bytes of prev][the block's source bytes].  The slot, h0 and the

@@ -54,6 +54,19 @@ STREAM_PART_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_len", "<
                                   ("flags", "<u4")])
 STREAM_CARRY_DTYPE = np.dtype([("crc", "<u4"), ("adler", "<u4"), ("total_in", "<u8"), ("total_out", "<u8"), ("parts", "<u4"), ("status", "<u4")])
 assert STREAM_PART_JOB_DTYPE.itemsize == 48 and STREAM_CARRY_DTYPE.itemsize == 32
+# a stream read in parts (include/nxz_engine.h: nxz_batch_inflate_streams_part)
+INFLATE_PART_TAIL = 288
+INFLATE_PHASE_HEADER, INFLATE_PHASE_BODY, INFLATE_PHASE_TRAILER, INFLATE_PHASE_DONE, INFLATE_PHASE_FAILED = range(5)
+INFLATE_PART_MORE, INFLATE_PART_DONE, INFLATE_PART_DST_FULL, INFLATE_PART_FAILED = range(4)
+INFLATE_PART_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("prev", "<u8"), ("src_len", "<u4"), ("dst_cap", "<u4"), ("prev_len", "<u4"),
+                                   ("flags", "<u4")])
+INFLATE_CARRY_DTYPE = np.dtype([("phase", "<u4"), ("hpos", "<u4"), ("hleft", "<u4"), ("hcrc", "<u4"), ("frame", FRAME_DTYPE), ("hfirst", "<u4"),
+                                ("sfbt", "<u4"), ("rem", "<u4"), ("dhtlen", "<u4"), ("subc", "<u4"), ("crc", "<u4"), ("adler", "<u4"),
+                                ("parts", "<u4"), ("tail_len", "<u4"), ("reserved", "<u4", (2,)), ("total_in", "<u8"), ("total_out", "<u8"),
+                                ("dht", "u1", (288,)), ("tail", "u1", (INFLATE_PART_TAIL,))])
+INFLATE_PART_RESULT_DTYPE = np.dtype([("cc", "<u4"), ("status", "<u4"), ("in_used", "<u4"), ("out_len", "<u4"), ("crc", "<u4"), ("adler", "<u4"),
+                                      ("reserved", "<u4", (2,))])
+assert INFLATE_PART_JOB_DTYPE.itemsize == 40 and INFLATE_CARRY_DTYPE.itemsize == 704 and INFLATE_PART_RESULT_DTYPE.itemsize == 32
 
 # multi-member gzip jobs (include/nxz_engine.h: nxz_batch_gzip_members_size / _decode)
 GZIP_MEMBER_DTYPE = np.dtype([("uoff", "<u8"), ("coff", "<u4"), ("clen", "<u4"), ("hdr_len", "<u4"), ("isize", "<u4"),
@@ -203,6 +216,7 @@ def load_library():
         L.nxz_deflate_stream_part_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32]
         L.nxz_batch_deflate_streams_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
+        L.nxz_batch_inflate_streams_part.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -494,6 +508,21 @@ class Engine:
         if results is None:
             results = t.empty(max(n, 1) * STREAM_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
         rc = self.L.nxz_batch_deflate_streams_part(self.ctx, fc, fmt, level, hist_max, jobs.ctypes.data if n else None, n,
+                                                   carry.data_ptr() if carry is not None else None, results.data_ptr(), self.stream_handle())
+        return rc, results
+
+    def inflate_stream_parts(self, fmt, jobs, carry, results=None):
+        """nxz_batch_inflate_streams_part on a HOST array of INFLATE_PART_JOB_DTYPE records (device addresses): a part of a stream each.
+        carry: a uint8 device tensor of len(jobs) INFLATE_CARRY_DTYPE records, read and written by the device (None is passed on as
+        NULL, which the call refuses); results_to_host(carry, INFLATE_CARRY_DTYPE) reads it.  Returns (rc, results): rc 0 / -errno,
+        results a uint8 device tensor of len(jobs) INFLATE_PART_RESULT_DTYPE records.  Asynchronous on torch's current stream: the
+        next part may be queued without a wait in between."""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, INFLATE_PART_JOB_DTYPE)
+        n = len(jobs)
+        if results is None:
+            results = t.empty(max(n, 1) * INFLATE_PART_RESULT_DTYPE.itemsize, dtype=t.uint8, device=self.dev)
+        rc = self.L.nxz_batch_inflate_streams_part(self.ctx, fmt, jobs.ctypes.data if n else None, n,
                                                    carry.data_ptr() if carry is not None else None, results.data_ptr(), self.stream_handle())
         return rc, results
 
