@@ -1,6 +1,6 @@
 // nxz_batch.cpp -- the raw batches of include/nxz_engine.h's device-resident interface: the compress and inflate batches and which
 // kernels they get, their dictionary forms, table generation, wrap and the pack forms, nxz_trim, stage timing and the diagnostics.
-// (The calls around them -- framed streams, sizes, members, one-stream deflate, BGZF and checkpoints -- are nxz_batch_framed.cpp's.)
+// (The calls around them are nxz_batch_framed.cpp's -- framed streams, sizes, members --, nxz_batch_streams.cpp's -- one-stream deflate and inflate -- and nxz_batch_ranges.cpp's -- BGZF and checkpoints.)
 #include "nxz_ctx.h"
 #include "nxz_inflate_part.h"
 

@@ -1,5 +1,5 @@
 // nxz_bgzf.hip -- BGZF random access on the device: a batch of byte ranges of a BGZF image, read through its member index
-// (nxz_bgzf_read_ranges; nxz_batch_framed.cpp runs the steps on the caller's stream and waits once, after the map).
+// (nxz_bgzf_read_ranges; nxz_batch_ranges.cpp runs the steps on the caller's stream and waits once, after the map).
 //
 // Map (nothing is decoded before the index has been checked):
 //   index_check_kernel   a thread a member: nxz_bgzf_member_size at coff[j] - coff[0] == coff[j+1] - coff[j], uoff

@@ -3,14 +3,14 @@
 // is the size walk (nxz_inflate_walk.h) with a hook at every block header, and a range read decodes its segments with
 // nxz_batch_decompress as jobs [window][source bytes] that resume inside a byte.
 //
-// The index, all on the caller's stream (nxz_batch_framed.cpp queues it, nothing waits for the host):
+// The index, all on the caller's stream (nxz_batch_ranges.cpp queues it, nothing waits for the host):
 //   index_kernel     one job per wavefront, one wavefront per workgroup, the long jobs first -- the shape of the size query
 //                    (nxz_inflate_size.hip) and of the member index (nxz_gzip_members.hip): the header by nxz_frame.h's parser, every
 //                    lane on the same bytes, then nxzs::walk, whose hook applies the checkpoint rule and stores the entry from lane 0;
 //                    the stream's record and the sentinel last.  LDS is the walk's; the accumulator lives in scalar registers.
 //   window_kernel    a workgroup per stored checkpoint (grid-stride): the min(uoff, 32768) bytes in front of uoff[k] from the job's
 //                    decoded output to the start of the checkpoint's slot, 16 bytes a lane where the slot's alignment allows.
-// A range read (nxz_batch_framed.cpp runs the steps and waits once, after the map -- the shape of nxz_bgzf_read_ranges, whose map, gather
+// A range read (nxz_batch_ranges.cpp runs the steps and waits once, after the map -- the shape of nxz_bgzf_read_ranges, whose map, gather
 // and zero kernels it uses as they are: nxz_bgzf.hip):
 //   check_kernel     a thread an entry: nxz_cp_entry_ok; any fault sets ctl[0] and every later kernel writes nothing
 //   (the range map and the scans of nxz_bgzf.hip over uoff: needed segments, each once, their list)

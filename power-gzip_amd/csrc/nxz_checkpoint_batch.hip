@@ -2,7 +2,7 @@
 // wave64).  The rules are nxz_checkpoint_batch.h's.  The batch's index is read as ONE index of n_jobs * (cp_cap + 1) entries in the
 // order the index calls wrote it, with a uoff of its own that never decreases (the rows' uoff on top of the bytes of the rows in
 // front); then the map, gather and zero kernels of nxz_bgzf.hip and the inmax and verdict kernels of nxz_checkpoint.hip work as they
-// stand, and nxz_batch_framed.cpp's driver waits once for the whole batch.  What is new here, in launch order:
+// stand, and nxz_batch_ranges.cpp's driver waits once for the whole batch.  What is new here, in launch order:
 //   rows_kernel      a thread an entry: the stream's record (at entry 0) and nxz_cpb_entry_ok against jobs[row].src_len; any fault
 //                    sets bad[row] -- the verdict is the row's, not the call's
 //   base_kernel      one workgroup: base[] = exclusive prefix sum of the good rows' extents (shuffles inside a wavefront, the

@@ -3,7 +3,7 @@
 // here: the index is the size walk (nxz_inflate_walk.h) with a hook that cuts between tokens, and a range read decodes its segments
 // with nxz_batch_decompress as jobs that resume inside a block.
 //
-// The index (nxz_batch_framed.cpp queues it, nothing waits for the host):
+// The index (nxz_batch_ranges.cpp queues it, nothing waits for the host):
 //   index_kernel     nxzcp::index_kernel's shape -- one job per wavefront, the header by nxz_frame.h's parser, then nxzs::walk -- with a
 //                    hook that gives the walk a budget of span bytes a segment: the walk calls it in front of the token that does
 //                    not fit (a stored run: behind the bytes that do), and lane 0 stores cbit / uoff / state; the stream's record

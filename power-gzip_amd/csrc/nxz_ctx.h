@@ -1,5 +1,5 @@
-// nxz_ctx.h -- what the host sources of libnxz_engine.so share (nxz_engine.cpp, nxz_batch.cpp, nxz_batch_framed.cpp, nxz_deflate_host.cpp): the
-// context, a stream's scratch with its buffer type and the rules for touching it, and a few helpers.  Private: not installed.
+// nxz_ctx.h -- what the host sources of libnxz_engine.so share (nxz_engine.cpp, nxz_batch.cpp, nxz_batch_framed.cpp,
+// nxz_batch_streams.cpp, nxz_batch_ranges.cpp, nxz_deflate_host.cpp): the context, a stream's scratch with its buffer type and the rules for touching it, and a few helpers.  Private: not installed.
 #ifndef NXZ_CTX_H
 #define NXZ_CTX_H
 #include <hip/hip_runtime.h>
@@ -88,7 +88,7 @@ enum ScratchBuf {
 	BUF_RNG,            // nxz_bgzf_read_ranges: the map's per-range and per-member arrays
 	BUF_RNG_SLOTS,      // ... a chunk of decoded members (16-byte aligned slots), their jobs, frames and results
 	BUF_RNG_BATCH,      // nxz_batch_checkpoint_read_ranges: the rows' verdicts and bases, the flat uoff, the ranges mapped onto it
-	BUF_STREAMS,        // nxz_batch_deflate_streams: descriptors, block prefix and state of the streams; jobs, results, owners, offsets and output slots of a chunk; nxz_batch_inflate_streams_part: descriptors and slot offsets; work, jobs, results, table slots and staging slots of a chunk
+	BUF_STREAMS,        // nxz_batch_streams.cpp (the layouts are carved there, nxz_streams_plan.h's nxz_carve); nxz_batch_deflate_streams and its forms: descriptors, block prefix and state of the streams; jobs, results, owners, offsets and output slots of a chunk; nxz_batch_inflate_streams_part: descriptors and slot offsets; work, jobs, results, table slots and staging slots of a chunk
 	BUF_GZIP_MEMBERS,   // nxz_batch_gzip_members_decode: the per-job plan, and the members as framed jobs with their owners, frames and results
 	BUF_COUNT
 };
@@ -277,7 +277,7 @@ struct nxz_dict {
 
 hipError_t stream_create_spread(hipStream_t *s, unsigned turn);   // nxz_engine.cpp
 size_t trim_compress_scratch();                                    // nxz_batch.cpp (nxz_trim)
-// nxz_batch.cpp, for the calls of nxz_batch_framed.cpp that run a raw batch or a kernel of its shape.
+// nxz_batch.cpp, for the calls of nxz_batch_framed.cpp, nxz_batch_streams.cpp and nxz_batch_ranges.cpp that run a raw batch or a kernel of its shape.
 // force: 0 -- the kernel by the batch's size and kind; 1 -- a stream per lane, any block type; 2 -- a stream per wavefront
 int batch_decompress(nxz_ctx_t *c, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_dht_t *dht_io, void *stream, int force);
 int batch_decompress_dict(nxz_ctx_t *c, const nxz_dict *dict, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, hipStream_t s);
@@ -287,6 +287,41 @@ int batch_compress_windowed(nxz_ctx_t *c, int fc, const uint8_t *win, size_t nwi
 // The jobs' indices by falling source length in BUF_ORDER of `s`, queued on `s` (NULL: none to be had, the jobs go as they come).
 // The caller holds the lease until its last launch that reads the order.
 const uint32_t *order_by_length_for(nxz_ctx *c, hipStream_t s, const nxz_batch_job_t *jobs, size_t n);
+
+// What the three families of calls around the raw batches share (nxz_batch_framed.cpp, nxz_batch_streams.cpp, nxz_batch_ranges.cpp).
+// A framed call holds frame_use[s] from its first kernel to its last:
+static inline std::mutex *frame_mutex(nxz_ctx_t *c, hipStream_t s)
+{
+	std::lock_guard<std::mutex> g(c->mtx);
+	return &c->frame_use[s];
+}
+// How every call goes on once its own arguments are checked.  rc: 1 -- go on, with the device selected, on `s`, frame_use[s] held
+// (`frame`) until this goes out of scope; else what the call returns now: -ENODEV in a forked child, 0 when it has no `work`.
+struct Entered {
+	hipStream_t s;
+	int rc;
+	std::unique_lock<std::mutex> use;
+	Entered(nxz_ctx_t *c, void *stream, bool work, bool frame = true) : s((hipStream_t)stream), rc(forked_child() ? -ENODEV : work ? 1 : 0)
+	{
+		if (rc != 1) return;
+		(void)hipSetDevice(c->device);
+		if (frame) use = std::unique_lock<std::mutex>(*frame_mutex(c, s));
+	}
+};
+// A single launch that walks the jobs a wavefront each: launch(order) under the stream's lease (the kernel reads the order), from 128
+// jobs on the long ones first, below that order NULL (the caller's order).  Nothing waits.
+template <class Launch>
+static inline int ordered_launch(nxz_ctx_t *c, hipStream_t s, const nxz_batch_job_t *jobs, size_t n, const char *what, Launch launch)
+{
+	const auto use = lease_scratch(c, s);
+	const uint32_t *order = n >= 128 ? order_by_length_for(c, s, jobs, n) : nullptr;
+	return launched(what, launch(order));
+}
+// nxz_batch_framed.cpp: header kernel -> the raw batch on the derived jobs -> trailer kernel, all on `s`; the caller holds frame_use[s]
+int framed_locked(nxz_ctx_t *c, int fmt, const nxz_batch_job_t *jobs, size_t n, nxz_batch_result_t *results, nxz_batch_frame_t *frames, hipStream_t s,
+		  const nxz_dict *dict = nullptr);
+// nxz_batch_ranges.cpp: the `force` of a raw batch whose jobs bring NXZ_JOB_SUSPEND_WHEN_FULL
+int fine_chunk_route();
 static inline uint64_t trace_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 #endif

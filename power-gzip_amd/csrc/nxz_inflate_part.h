@@ -1,5 +1,5 @@
 // nxz_inflate_part.h -- the rules of nxz_batch_inflate_streams_part (include/nxz_engine.h: a stream read in parts, a device buffer a
-// part) as plain code that compiles for the device (nxz_inflate_part.hip), for the engine's host side (nxz_batch_framed.cpp) and for a
+// part) as plain code that compiles for the device (nxz_inflate_part.hip), for the engine's host side (nxz_batch_streams.cpp) and for a
 // host test program (tests/native/inflate_part_host.cpp).  Every function works on the carry record where it lies (704 bytes: never
 // a copy).  The field rules of the headers and the trailer's comparison are nxz_frame.h's; here is what a stream in parts adds:
 //

@@ -1,5 +1,5 @@
 // nxz_streams.h -- the rules of nxz_batch_deflate_streams (include/nxz_engine.h: a device buffer of any length -> one raw, zlib or
-// gzip stream) as plain code that compiles for the device (nxz_streams.hip), for the engine's host side (nxz_batch_framed.cpp) and for a
+// gzip stream) as plain code that compiles for the device (nxz_streams.hip), for the engine's host side (nxz_batch_streams.cpp) and for a
 // host test program (tests/native/streams_host.cpp).
 //
 //   the block plan   a buffer is cut as nxz_deflate_host_hist cuts it: with a window of H = min(hist_max & ~15, 32768) bytes a

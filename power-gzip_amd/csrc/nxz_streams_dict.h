@@ -1,6 +1,6 @@
 // nxz_streams_dict.h -- the rules of nxz_batch_deflate_streams_dict (include/nxz_engine.h: a device buffer of any length -> one raw or
 // zlib stream whose first block sees a shared preset dictionary) as plain code that compiles for the device (nxz_streams_dict.hip),
-// for the engine's host side (nxz_batch_framed.cpp) and for a host test program (tests/native/streams_dict_host.cpp).  What is
+// for the engine's host side (nxz_batch_streams.cpp) and for a host test program (tests/native/streams_dict_host.cpp).  What is
 // not here is nxz_streams.h's: the block plan, the trailer, the checksum joins.
 //
 //   the first window   block 0 sees the last h0 = min(H, len) & ~15 bytes of the dictionary, H = nxz_streams_window(hist_max): the

@@ -1,6 +1,6 @@
 // nxz_streams_index.hip -- the checkpoint index of nxz_batch_deflate_streams_indexed (include/nxz_engine.h), written while the streams
 // are laid out: no stream is walked, the block headers are where layout put them.  The rules are nxz_streams_index.h; the kernels of
-// nxz_streams.hip run as they are, these go beside them on the same stream (nxz_batch_framed.cpp queues them):
+// nxz_streams.hip run as they are, these go beside them on the same stream (nxz_batch_streams.cpp queues them):
 //
 //   prologue   (behind the plain prologue) a thread per stream: checkpoint 0, which always stands behind the framing's header, and the
 //              stream's running index state -- or `on = 0` for a stream that gets no index (refused, or too long for the row format)

@@ -1,5 +1,5 @@
 // nxz_streams_part.h -- the rules of nxz_batch_deflate_streams_part (include/nxz_engine.h: a stream written in parts, a device buffer a
-// part) as plain code that compiles for the device (nxz_streams_part.hip), for the engine's host side (nxz_batch_framed.cpp) and for a
+// part) as plain code that compiles for the device (nxz_streams_part.hip), for the engine's host side (nxz_batch_streams.cpp) and for a
 // host test program (tests/native/streams_part_host.cpp).  What is not here is nxz_streams.h's: the block plan, the header and
 // trailer bytes, the checksum joins.
 //

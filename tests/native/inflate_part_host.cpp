@@ -6,6 +6,8 @@
 //   trailer <fmt> <crc> <adler> <total_out> <hex> <piece lengths ...>
 //   stale <fmt> <tail_len> <n>
 //   close <told> <hist> <body> <src_len> <cap> <spbc> <subc> <sfbt> <tebc> <cc> <tpbc>   source byte k of [tail][part from body] is k & 0xff
+//   cut <scratch> <max_streams> <bound_0> <bound_1> ...   the engine's own cut of a batch into chunks (nxz_streams_plan.h): "m off_0 .. off_m"
+//                                                        per chunk, m read back from off[] as the engine reads it, then "max_cnt max_bytes", all on one line joined by " | "
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "nxz_inflate_part.h"
+#include "nxz_streams_plan.h"
 
 static std::vector<uint8_t> unhex(const std::string &h)
 {
@@ -122,6 +125,23 @@ int main()
 			for (uint32_t k = 0; k < c->tail_len; k++) printf(" %u", c->tail[k]);
 			printf("\n");
 			delete c; free(buf);
+		} else if (cmd == "cut") {
+			unsigned long long scratch, v; uint32_t max_streams;
+			in >> scratch >> max_streams;
+			std::vector<uint64_t> bound;
+			while (in >> v) bound.push_back(v);
+			// off[] in a buffer of exactly the 2 n entries the engine sets aside: a write beyond it is the sanitizer's
+			uint64_t *off = (uint64_t *)malloc(2 * bound.size() * sizeof(uint64_t) + 1);
+			const nxz_plan_cut p = nxz_plan_inflate_cut(bound.size(), scratch, max_streams, off, [&](size_t i) { return bound[i]; });
+			for (size_t e0 = 0; e0 < p.entries;) {
+				const uint32_t m = nxz_plan_cut_streams(off, e0, p.entries);
+				printf("%u", m);
+				for (uint32_t k = 0; k <= m; k++) printf(" %llu", (unsigned long long)off[e0 + k]);
+				printf(" | ");
+				e0 += m + 1;
+			}
+			printf("%u %llu\n", p.max_cnt, (unsigned long long)p.max_bytes);
+			free(off);
 		} else {
 			fprintf(stderr, "unknown command: %s\n", cmd.c_str());
 			return 2;

@@ -8,14 +8,14 @@
 //   bound src_len hist_max fmt                  -> "bound plain_bound": this call's and nxz_batch_deflate_streams'
 //   refuse src dst src_len dst_cap hist_max fmt -> the completion code
 //   order C blocks_0 blocks_1 ...               -> the launch order of every chunk of C blocks of a batch whose stream i has blocks_i
-//                                                  blocks, found as the host (nxz_batch_framed.cpp) and the expand kernel find it: a
-//                                                  line "nf pos_0 pos_1 ..." per chunk
+//                                                  blocks, found as the host finds it (the engine's own plan, nxz_streams_plan.h, run here)
+//                                                  and the expand kernel: a line "nf pos_0 pos_1 ..." per chunk
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "nxz_streams_dict.h"
+#include "nxz_streams_plan.h"
 
 static uint32_t owner_of(const std::vector<uint32_t> &first, uint32_t g)       // (nxz_streams_dev.h)
 {
@@ -33,24 +33,17 @@ static void order(char *args)
 	for (char *p = strtok(args, " \n"); p; p = strtok(nullptr, " \n")) v.push_back((uint32_t)strtoul(p, nullptr, 10));
 	const uint32_t C = v[0], n = (uint32_t)v.size() - 1;
 	std::vector<uint32_t> first(n + 1), nz(n + 1);
-	uint32_t total = 0, with = 0;
-	for (uint32_t i = 0; i < n; i++) { first[i] = total; nz[i] = with; total += v[1 + i]; with += v[1 + i] ? 1 : 0; }
-	first[n] = total; nz[n] = with;
-	uint32_t i_lo = 0;
-	for (uint32_t b0 = 0; b0 < total; b0 += C) {
-		const uint32_t m = total - b0 < C ? total - b0 : C;
-		while (first[i_lo + 1] <= b0) i_lo++;
-		uint32_t i_hi = i_lo;
-		while (first[i_hi + 1] < b0 + m) i_hi++;
-		const uint32_t nz_b0 = nxz_streams_dict_firsts_before(nz[i_lo], b0 - first[i_lo]), nf = nxz_streams_dict_firsts_before(nz[i_hi], 1) - nz_b0;
-		printf("%u", nf);
-		for (uint32_t t = 0; t < m; t++) {
-			const uint32_t g = b0 + t, i = owner_of(first, g);
+	const int64_t total = nxz_plan_prefix(n, first.data(), nz.data(), [&](size_t i, bool *) { return v[1 + i]; });
+	if (total < 0) exit(5);
+	for (nxz_plan_chunk c = {0, 0, 0, 0}; nxz_plan_next_chunk(first.data(), (uint32_t)total, C, &c);) {
+		const nxz_plan_count f = nxz_plan_dict_firsts(first.data(), nz.data(), c);
+		printf("%u", f.inside);
+		for (uint32_t t = 0; t < c.m; t++) {
+			const uint32_t g = c.b0 + t, i = owner_of(first, g);
 			const uint64_t k = g - first[i];
-			printf(" %u", nxz_streams_dict_launch_pos(t, k, nxz_streams_dict_firsts_before(nz[i], k) - nz_b0, nf));
+			printf(" %u", nxz_streams_dict_launch_pos(t, k, nxz_streams_dict_firsts_before(nz[i], k) - f.before, f.inside));
 		}
 		printf("\n");
-		i_lo = i_hi;
 	}
 }
 

@@ -9,8 +9,8 @@
 //                                                    -> the carry a part starts from (`first`: 1 with NXZ_PART_FIRST) and the one it
 //                                                       leaves: "crc adler total_in total_out parts status" twice
 //   frame fmt level flags crc adler total_len        -> "hex hex": the header and the trailer bytes this part writes ("-" for none)
-//   plan C staged_0 blocks_0 staged_1 blocks_1 ...   -> per chunk of C blocks "sg_b0 nst q..." as the host (nxz_batch_framed.cpp) and the
-//                                                       expand kernel find them: the staged first blocks in front of the chunk, inside
+//   plan C staged_0 blocks_0 staged_1 blocks_1 ...   -> per chunk of C blocks "sg_b0 nst q..." as the host finds them (the engine's own plan,
+//                                                       nxz_streams_plan.h, run here) and the expand kernel: the staged first blocks in front of the chunk, inside
 //                                                       it, and the slot of each staged block of the chunk in the batch's order
 #include <cinttypes>
 #include <cstdio>
@@ -18,6 +18,7 @@
 #include <cstring>
 #include <vector>
 #include "nxz_streams_part.h"
+#include "nxz_streams_plan.h"
 
 static uint32_t owner_of(const std::vector<uint32_t> &first, uint32_t g)       // (nxz_streams_dev.h)
 {
@@ -35,23 +36,16 @@ static void plan(char *args)
 	for (char *p = strtok(args, " \n"); p; p = strtok(nullptr, " \n")) v.push_back((uint32_t)strtoul(p, nullptr, 10));
 	const uint32_t C = v[0], n = ((uint32_t)v.size() - 1) / 2;
 	std::vector<uint32_t> first(n + 1), sg(n + 1);
-	uint32_t total = 0, staged = 0;
-	for (uint32_t i = 0; i < n; i++) { first[i] = total; sg[i] = staged; total += v[2 + 2 * i]; staged += v[2 + 2 * i] && v[1 + 2 * i] ? 1 : 0; }
-	first[n] = total; sg[n] = staged;
-	uint32_t i_lo = 0;
-	for (uint32_t b0 = 0; b0 < total; b0 += C) {
-		const uint32_t m = total - b0 < C ? total - b0 : C;
-		while (first[i_lo + 1] <= b0) i_lo++;
-		uint32_t i_hi = i_lo;
-		while (first[i_hi + 1] < b0 + m) i_hi++;
-		const uint32_t sg_b0 = first[i_lo] < b0 ? sg[i_lo + 1] : sg[i_lo], nst = sg[i_hi + 1] - sg_b0;
-		printf("%u %u", sg_b0, nst);
-		for (uint32_t t = 0; t < m; t++) {
-			const uint32_t g = b0 + t, i = owner_of(first, g);
-			if (g == first[i] && sg[i + 1] != sg[i]) printf(" %u", sg[i] - sg_b0);
+	const int64_t total = nxz_plan_prefix(n, first.data(), sg.data(), [&](size_t i, bool *staged) { *staged = v[1 + 2 * i] != 0; return v[2 + 2 * i]; });
+	if (total < 0) exit(5);
+	for (nxz_plan_chunk k = {0, 0, 0, 0}; nxz_plan_next_chunk(first.data(), (uint32_t)total, C, &k);) {
+		const nxz_plan_count c = nxz_plan_part_staged(first.data(), sg.data(), k);
+		printf("%u %u", c.before, c.inside);
+		for (uint32_t t = 0; t < k.m; t++) {
+			const uint32_t g = k.b0 + t, i = owner_of(first, g);
+			if (g == first[i] && sg[i + 1] != sg[i]) printf(" %u", sg[i] - c.before);
 		}
 		printf("\n");
-		i_lo = i_hi;
 	}
 }
 

@@ -215,3 +215,62 @@ def test_tail_and_in_used_over_brute_forced_positions(host):
         assert st == MORE or used < src_len, c
         kinds.add((st, used == 0 and st == DST_FULL))
     assert kinds == {"failed", (MORE, False), (DST_FULL, False), (DST_FULL, True)}
+
+
+def slot_bound(prev_len, src_len):
+    """nxz_inflate_part_slot_bound: the largest window, a full tail of 288 bytes, the part, rounded up to 16"""
+    return (min(prev_len, 32768) + 288 + src_len + 15) & ~15
+
+
+def greedy_cut(bounds, scratch, max_streams):
+    """the rule in plain Python: a chunk ends in front of the stream that would carry it beyond the scratch, or at max_streams"""
+    chunks, cur = [], []
+    for b in bounds:
+        if cur and (sum(cur) + b > scratch or len(cur) == max_streams):
+            chunks.append(cur)
+            cur = []
+        cur.append(b)
+    return chunks + [cur]
+
+
+def test_the_cut_into_chunks_against_a_greedy_cut(host):
+    """The engine's own cut (nxz_plan_inflate_cut, nxz_streams_plan.h) and its read-back of a chunk's stream count from off[]
+    (nxz_plan_cut_streams).  The read-back ends a chunk at the next 0, so it would stop short in a chunk whose SECOND entry is 0: a
+    first stream with bound 0.  nxz_inflate_part_slot_bound cannot return 0 -- it holds a full tail, 288 bytes, for any part, and adds
+    in 64 bits -- so every bound here is at least 288, as every bound the engine sees is."""
+    rnd = random.Random(7)
+    big = 1 << 30
+    cases = [("equal", 1000, 16384, [304] * 10),
+             ("one larger than the scratch", 1000, 16384, [304, 5008, 304, 304]), ("the larger one first", 1000, 16384, [5008, 304]),
+             ("the larger one last", 1000, 16384, [304, 5008]),
+             ("exactly the scratch", 1008, 16384, [304, 304, 400]), ("one byte over", 1007, 16384, [304, 304, 400]),
+             ("a single stream", 1000, 16384, [304]), ("a single stream larger than the scratch", 100, 16384, [304])]
+    cases += [("max_streams %d" % k, big, k, [304] * 7) for k in (1, 2, 3)]
+    for scratch in (1, 4096, 1 << 20):
+        bounds = [slot_bound(rnd.choice((0, 5, 40000)), rnd.choice((0, 1, 100, 3000, 70000, 300000))) for _ in range(200)]
+        cases.append(("random, scratch %d" % scratch, scratch, 16384, bounds))
+        cases.append(("random, scratch %d, 5 streams" % scratch, scratch, 5, bounds))
+    assert min(b for c in cases for b in c[3]) >= 288 == slot_bound(0, 0)
+    out = host(["cut %d %d %s" % (scratch, most, " ".join(map(str, bounds))) for _, scratch, most, bounds in cases])
+    cut_anywhere = set()
+    for (name, scratch, most, bounds), line in zip(cases, out):
+        *chunks, maxima = line.split(" | ")
+        chunks = [[int(x) for x in ch.split()] for ch in chunks]
+        want = greedy_cut(bounds, scratch, most)
+        # every stream in exactly one chunk, the chunks contiguous and in order: their bounds, joined, are the batch's
+        got = [[b - a for a, b in zip(ch[1:], ch[2:])] for ch in chunks]
+        assert [b for g in got for b in g] == bounds, name
+        assert got == want, name
+        for ch, w in zip(chunks, want):
+            m, off = ch[0], ch[1:]
+            assert m == len(w) == len(off) - 1, name                   # the count read back from off[] is the count the cut made
+            assert off[0] == 0 and off == sorted(off) and off[-1] == sum(w), name
+            assert m == 1 or off[-1] <= scratch, name
+            assert m <= most, name
+        assert [int(x) for x in maxima.split()] == [max(len(w) for w in want), max(sum(w) for w in want)], name
+        cut_anywhere.add(len(want) > 1)
+    # what the named cases are there for, worked out by hand: 304 x 3 a chunk; 304 | 5008 | 304 304; no cut at 1008, one at 1007
+    assert [greedy_cut(c[3], c[1], c[2]) for c in cases[1:6]] == [[[304], [5008], [304, 304]], [[5008], [304]], [[304], [5008]], [[304, 304, 400]],
+                                                                  [[304, 304], [400]]]
+    assert [[len(w) for w in greedy_cut(c[3], c[1], c[2])] for c in (cases[0], *cases[8:11])] == [[3, 3, 3, 1], [1] * 7, [2, 2, 2, 1], [3, 3, 1]]
+    assert cut_anywhere == {False, True}
