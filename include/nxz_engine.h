@@ -927,6 +927,49 @@ int nxz_batch_inflate_streams_part(nxz_ctx_t *ctx, int fmt /* NXZ_FMT_RAW, ZLIB,
 				   nxz_inflate_carry_t *carry /* DEVICE, n, in/out */,
 				   nxz_inflate_part_result_t *results /* DEVICE, n */, void *stream);
 
+/* The byte-shuffle filter (additive): what stands between a numeric Zarr or HDF5 chunk and its deflate stream.  HDF5's standard
+ * pipeline for chunked numeric datasets is H5Z_FILTER_SHUFFLE followed by deflate, Zarr's numcodecs.Shuffle + zlib; the rule here is
+ * HDF5's.  With N = len / elem and r = len % elem, nxz_batch_shuffle writes dst[j * N + i] = src[i * elem + j] for i < N, j < elem --
+ * byte 0 of every element, then byte 1 of every element, ... -- and copies the r leftover bytes unchanged to dst[N * elem ..].
+ * nxz_batch_unshuffle is the exact inverse under the same (len, elem).  elem == 1 and len < elem are plain copies.
+ * Write side: shuffle, then nxz_batch_deflate_streams(NXZ_FMT_ZLIB) on the shuffled buffer; read side: nxz_batch_decompress_framed,
+ * then unshuffle with the chunk's known size and element size.
+ * jobs is a HOST array and may be reused when the call returns; status is a DEVICE array: status[i] = 0, or NXZ_CC_INVALID_OP for
+ * src or dst NULL with len != 0, elem == 0 or elem > NXZ_SHUFFLE_ELEM_MAX, reserved != 0, or byte ranges that overlap (src == dst
+ * included; ranges that only touch are taken).  A refused job leaves dst untouched and its neighbours unaffected.
+ * On the device (power-gzip_amd/csrc/nxz_shuffle.hip, the rules in nxz_shuffle.h): one grid over the tiles of all jobs, whatever mix
+ * of lengths -- the host's one pass writes the tile prefix into pinned staging of the stream's scratch, a workgroup finds its
+ * (job, tile) there.  A tile is nxz_shuffle_tile_elems(elem) elements: the most that fit 16 KiB, rounded down to a multiple of 16.
+ * It is transposed through LDS (20 KiB of planes and a 1 KiB table at the most), with loads and stores of 16 bytes a lane on 16-byte
+ * boundaries and a byte-wise head and tail around them for every plane's run: dst + j * N has whatever alignment N leaves it.  elem 2,
+ * 4, 8 and 16 run with the element size as a constant; every other size up to 256, the copies included, takes one generic path.
+ * Asynchronous on `stream`: no host wait, no device allocation once the stream's scratch has grown, two launches whatever n is.
+ * Returns 0; -EINVAL (ctx NULL, jobs or status NULL with n != 0); -ENODEV in a forked child; -E2BIG for n >= 2^31 (or 2^31 tiles:
+ * 32 TiB); -ENOMEM when scratch cannot be had.  n == 0 returns 0 and launches nothing.
+ * Not part of this call: the transpose fused into the LZ77 kernel's load or the inflate kernels' flush -- a pass of its own costs
+ * two sweeps of memory beside a codec that runs at a few percent of memory bandwidth; bit-shuffle (Blosc's); in-place operation.
+ * Speed (tools/bench_shuffle.py, profiles/r26_shuffle.txt; medians of 5 runs taken in turn, every route within 2.5 % of its median), as
+ * the time of nxz_copy_device on the same total bytes.  4096 buffers of 1 MiB (copy 1.55 ms): shuffle 0.93 / 0.92 / 0.94 and unshuffle
+ * 1.00 / 1.01 / 1.01 for elem 2 / 4 / 8 -- the pass is memory-bound, 2.5 to 2.8 TiB/s of source bytes; the generic path (elem 12) 1.28
+ * and 2.64.  65 536 buffers of 64 KiB (copy 1.65 ms): 1.10 and 1.18 to 1.20 for elem 2 / 4 / 8, generic 1.63 and 3.02.  The generic
+ * unshuffle gathers its 16 bytes a lane with a step from byte to byte that the constant paths do with a mask; it is the one form far
+ * from the copy.  Beside the codec (1024 buffers of 1 MiB, zlib, DHTGEN, hist_max 0): shuffle + nxz_batch_deflate_streams against that
+ * call alone takes 1.11 of the time and leaves 0.767 of the compressed bytes on float32 random walks (0.662 against 0.863 of the
+ * source), 1.18 of the time and 0.916 of the bytes on bf16 N(0, 0.02) weights (0.715 against 0.780).  The pass itself is 0.4 ms of
+ * those 1.0 and 1.5 ms; the rest is the codec on other bytes. */
+#define NXZ_SHUFFLE_ELEM_MAX 256
+typedef struct nxz_shuffle_job {      /* HOST array, as nxz_stream_job_t: may be reused when the call returns */
+	const uint8_t *src;           /* DEVICE, any alignment */
+	uint8_t       *dst;           /* DEVICE, any alignment, len bytes; must not overlap src */
+	uint64_t       len;           /* any length, 0 included */
+	uint32_t       elem;          /* element size in bytes, 1 .. NXZ_SHUFFLE_ELEM_MAX */
+	uint32_t       reserved;      /* 0 */
+} nxz_shuffle_job_t;
+int nxz_batch_shuffle  (nxz_ctx_t *ctx, const nxz_shuffle_job_t *jobs /* HOST */, size_t n, uint32_t *status /* DEVICE, n */, void *stream);
+int nxz_batch_unshuffle(nxz_ctx_t *ctx, const nxz_shuffle_job_t *jobs /* HOST */, size_t n, uint32_t *status /* DEVICE, n */, void *stream);
+/* the elements a workgroup takes of a job with this element size (0 for an elem the calls refuse) */
+uint32_t nxz_shuffle_tile_elems(uint32_t elem);
+
 /* ------------------------------------------------------------------------
  * BGZF random access: the member index and batched range reads
  * ---------------------------------------------------------------------- */

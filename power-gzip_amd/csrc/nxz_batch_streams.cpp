@@ -6,6 +6,7 @@
 #include "nxz_streams_index.h"
 #include "nxz_streams_part.h"
 #include "nxz_inflate_part.h"
+#include "nxz_shuffle.h"
 
 // ---------------------------------------------------------------------------
 // One stream per device buffer (nxz_streams.hip, the rules in nxz_streams.h).  The host makes one pass over the streams -- the
@@ -340,4 +341,47 @@ extern "C" int nxz_batch_inflate_streams_part(nxz_ctx_t *c, int fmt, const nxz_i
 		i0 += m; e0 += m + 1;
 	}
 	return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The byte-shuffle filter (nxz_shuffle.hip, the rules in nxz_shuffle.h): the same pinned staging and upload, BUF_STREAMS under
+// frame_use[s], everything on `s` and no host wait.  The host's one pass (nxz_shuffle_plan_batch) writes what the kernel reads of a job,
+// the tile prefix and the statuses -- every refusal is the host's to see -- and all three go up in one copy; then the statuses' copy
+// and one grid over the tiles.
+// ---------------------------------------------------------------------------
+extern "C" uint32_t nxz_shuffle_tile_elems(uint32_t elem)
+{
+	return elem && elem <= NXZ_SHUFFLE_ELEM_MAX ? nxz_shuffle_tile_elems_of(elem) : 0;
+}
+
+static int batch_shuffle(nxz_ctx_t *c, const nxz_shuffle_job_t *jobs, size_t n, uint32_t *status, void *stream, int undo)
+{
+	if (!c || (n && (!jobs || !status))) return -EINVAL;
+	const Entered in(c, stream, n != 0);
+	if (in.rc != 1) return in.rc;
+	if (n >= (1u << 31)) return -E2BIG;
+	hipStream_t s = in.s;
+	nxz_carve lay;
+	lay.take(n * sizeof(nxz_shuffle_plan_t));
+	const size_t o_first = lay.take((n + 1) * sizeof(uint32_t)), o_st = lay.take(n * sizeof(uint32_t)), up_bytes = lay.end;
+	uint8_t *st_h = nullptr;
+	hipEvent_t st_ev = nullptr;
+	int rc = streams_staging(c, s, up_bytes, &st_h, &st_ev);
+	if (rc) return rc;
+	const int64_t tiles = nxz_shuffle_plan_batch(jobs, n, (nxz_shuffle_plan_t *)st_h, (uint32_t *)(st_h + o_first), (uint32_t *)(st_h + o_st));
+	if (tiles < 0) return -E2BIG;
+	const uint8_t *const d = streams_upload(c, s, lay.end, st_h, up_bytes, st_ev, &rc);
+	if (!d) return rc;
+	return launched("shuffle launch", nxz_launch_shuffle((const nxz_shuffle_plan_t *)d, (const uint32_t *)(d + o_first), (const uint32_t *)(d + o_st),
+							     (uint32_t)n, (uint32_t)tiles, undo, status, s));
+}
+
+extern "C" int nxz_batch_shuffle(nxz_ctx_t *c, const nxz_shuffle_job_t *jobs, size_t n, uint32_t *status, void *stream)
+{
+	return batch_shuffle(c, jobs, n, status, stream, 0);
+}
+
+extern "C" int nxz_batch_unshuffle(nxz_ctx_t *c, const nxz_shuffle_job_t *jobs, size_t n, uint32_t *status, void *stream)
+{
+	return batch_shuffle(c, jobs, n, status, stream, 1);
 }

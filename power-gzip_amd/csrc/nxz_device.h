@@ -288,6 +288,11 @@ int nxz_launch_inflate_part_stage(const nxz_inflate_part_job_t *desc, const nxz_
 int nxz_launch_inflate_part_close(const nxz_inflate_part_job_t *desc, uint32_t m, nxz_inflate_carry_t *carry, const nxz_batch_job_t *jobs,
 				  const nxz_batch_result_t *dres, const nxz_batch_dht_t *dht, const nxz_inflate_part_work_t *work,
 				  nxz_inflate_part_result_t *results, hipStream_t stream);
+/* nxz_shuffle.hip: the byte-shuffle filter (nxz_batch_shuffle / nxz_batch_unshuffle; nxz_shuffle.h has the rules).  plan[n], first[n + 1]
+ * and st[n] are the host's one pass (nxz_shuffle_plan_batch) in device memory, tiles = first[n]: st goes to status, one grid takes the tiles */
+struct nxz_shuffle_plan;
+int nxz_launch_shuffle(const struct nxz_shuffle_plan *plan, const uint32_t *first, const uint32_t *st, uint32_t n, uint32_t tiles, int undo,
+		       uint32_t *status, hipStream_t stream);
 int nxz_inflate_wg_reasons(const uint8_t *wg_ws, uint32_t *out16);
 int nxz_inflate_wg_prof(const uint8_t *wg_ws, unsigned long long *out12);
 }

@@ -68,6 +68,11 @@ INFLATE_PART_RESULT_DTYPE = np.dtype([("cc", "<u4"), ("status", "<u4"), ("in_use
                                       ("reserved", "<u4", (2,))])
 assert INFLATE_PART_JOB_DTYPE.itemsize == 40 and INFLATE_CARRY_DTYPE.itemsize == 704 and INFLATE_PART_RESULT_DTYPE.itemsize == 32
 
+# the byte-shuffle filter (include/nxz_engine.h: nxz_batch_shuffle / nxz_batch_unshuffle)
+SHUFFLE_ELEM_MAX = 256
+SHUFFLE_JOB_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u8"), ("elem", "<u4"), ("reserved", "<u4")])
+assert SHUFFLE_JOB_DTYPE.itemsize == 32
+
 # multi-member gzip jobs (include/nxz_engine.h: nxz_batch_gzip_members_size / _decode)
 GZIP_MEMBER_DTYPE = np.dtype([("uoff", "<u8"), ("coff", "<u4"), ("clen", "<u4"), ("hdr_len", "<u4"), ("isize", "<u4"),
                               ("check", "<u4"), ("status", "<u4")])
@@ -217,6 +222,10 @@ def load_library():
         L.nxz_batch_deflate_streams_part.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                      C.c_void_p, C.c_void_p]
         L.nxz_batch_inflate_streams_part.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.nxz_batch_shuffle.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_batch_unshuffle.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.nxz_shuffle_tile_elems.restype = C.c_uint32
+        L.nxz_shuffle_tile_elems.argtypes = [C.c_uint32]
         L.nxz_batch_unpack_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]
         L.nxz_bgzf_index.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_void_p]
@@ -620,6 +629,40 @@ class Engine:
             rc, results = self.deflate_stream_jobs_dict(fc, fmt, d, j, hist_max=hist_max, level=level)
         self._check(rc, "nxz_batch_deflate_streams" if d is None else "nxz_batch_deflate_streams_dict")
         return out, offsets, results
+
+    # ---- the byte-shuffle filter of HDF5 / numcodecs: byte j of every element, plane after plane ----
+    def shuffle_tile_elems(self, elem):
+        """nxz_shuffle_tile_elems: the elements a workgroup takes of a job with this element size"""
+        return self.L.nxz_shuffle_tile_elems(elem)
+
+    def shuffle(self, jobs, status=None, undo=False):
+        """nxz_batch_shuffle (undo: nxz_batch_unshuffle) on a HOST array of SHUFFLE_JOB_DTYPE records (device addresses).  Returns
+        (rc, status): rc 0 / -errno, status a uint32 device tensor of len(jobs) entries (False is passed on as NULL, which the call
+        refuses).  Asynchronous on torch's current stream."""
+        t = self.torch
+        jobs = np.ascontiguousarray(jobs, SHUFFLE_JOB_DTYPE)
+        n = len(jobs)
+        if status is None:
+            status = t.empty(max(n, 1), dtype=t.int32, device=self.dev)
+        f = self.L.nxz_batch_unshuffle if undo else self.L.nxz_batch_shuffle
+        rc = f(self.ctx, jobs.ctypes.data if n else None, n, status.data_ptr() if status is not False else None, self.stream_handle())
+        return rc, status
+
+    def shuffle_bufs(self, bufs, elem, undo=False):
+        """bufs: uint8 device tensors of any length and alignment -> their shuffled (undo: unshuffled) forms with element size
+        `elem`.  Returns (out, offsets, status): buffer i's result is out[offsets[i]:offsets[i] + bufs[i].numel()] (a uint8 device
+        tensor, every result 16-byte aligned in it); status as shuffle.  Asynchronous."""
+        t = self.torch
+        offsets = np.zeros(len(bufs) + 1, np.int64)
+        offsets[1:] = np.cumsum([(b.numel() + 15) & ~15 for b in bufs])
+        out = t.empty(max(int(offsets[-1]), 1), dtype=t.uint8, device=self.dev)
+        j = np.zeros(len(bufs), SHUFFLE_JOB_DTYPE)
+        for i, b in enumerate(bufs):
+            assert b.dtype == t.uint8 and b.is_contiguous() and b.device == out.device
+            j[i] = (b.data_ptr() if b.numel() else 0, out.data_ptr() + int(offsets[i]), b.numel(), elem, 0)
+        rc, status = self.shuffle(j, undo=undo)
+        self._check(rc, "nxz_batch_unshuffle" if undo else "nxz_batch_shuffle")
+        return out, offsets, status
 
     def frames_to_host(self, frames):
         self.torch.cuda.synchronize(self.dev)

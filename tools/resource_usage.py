@@ -6,7 +6,7 @@ kernel went from 96 to 99 VGPRs unnoticed and lost a wavefront per SIMD: 72.9 ->
 import json, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "power-gzip_amd", "csrc")
-FILES = ["nxz_lz77.hip", "nxz_symcount.hip", "nxz_encode.hip", "nxz_dhtgen.hip", "nxz_inflate.hip", "nxz_inflate_lanes.hip", "nxz_inflate_wg.hip", "nxz_inflate_cut.hip", "nxz_inflate_size.hip", "nxz_inflate_verify.hip", "nxz_gzip_members.hip", "nxz_checkpoint.hip", "nxz_checkpoint_fine.hip", "nxz_checkpoint_build.hip", "nxz_checkpoint_batch.hip", "nxz_misc.hip", "nxz_streams.hip", "nxz_streams_dict.hip", "nxz_streams_index.hip", "nxz_streams_part.hip", "nxz_inflate_part.hip", "nxz_frame.hip", "nxz_bgzf.hip", "nxz_blockfind.hip"]
+FILES = ["nxz_lz77.hip", "nxz_symcount.hip", "nxz_encode.hip", "nxz_dhtgen.hip", "nxz_inflate.hip", "nxz_inflate_lanes.hip", "nxz_inflate_wg.hip", "nxz_inflate_cut.hip", "nxz_inflate_size.hip", "nxz_inflate_verify.hip", "nxz_gzip_members.hip", "nxz_checkpoint.hip", "nxz_checkpoint_fine.hip", "nxz_checkpoint_build.hip", "nxz_checkpoint_batch.hip", "nxz_misc.hip", "nxz_streams.hip", "nxz_streams_dict.hip", "nxz_streams_index.hip", "nxz_streams_part.hip", "nxz_inflate_part.hip", "nxz_shuffle.hip", "nxz_frame.hip", "nxz_bgzf.hip", "nxz_blockfind.hip"]
 
 
 def demangle(names):
