@@ -58,6 +58,70 @@ def index(image):
     return coff, uoff
 
 
+MAGIC = b"\x1f\x8b\x08\x04"
+
+
+def candidates(image):
+    """[(position, size)]: every position at which member_size is non-zero, in order -- what the discovery's scan must find"""
+    out, p = [], image.find(MAGIC)
+    while p >= 0:
+        sz = member_size(image, p)
+        if sz:
+            out.append((p, sz))
+        p = image.find(MAGIC, p + 1)
+    return out
+
+
+class Discovery:
+    """what nxz_launch_bgzf_discover / nxz_launch_bgzf_coff promise for one image at one cap and max_members (discover)"""
+
+
+def discover(image, cap, max_members):
+    """Everything the launcher promises, by plain loops (the successor of a candidate is looked for by walking on through the list):
+      ctl          [candidates C, members L, bytes the members cover, sum of ISIZE]
+      complete     C <= cap.  When it is False ONLY ctl[0] and pos / size are promised: the caller runs again with cap = C
+      pos, size    of the first min(C, cap) candidates
+      written      0 < L <= max_members.  When it is False offsets, jobs and coff are UNWRITTEN and ctl[3] is 0
+      offsets      [0 .. L]: the running sum of ISIZE (64-bit)
+      members      per member (src offset, src_len, dst offset, dst_cap)
+      coff         [0 .. L]: where member j starts; coff[L] = the bytes covered"""
+    d = Discovery()
+    cand = candidates(image)
+    C = len(cand)
+    d.complete = C <= cap
+    d.pos = [p for p, _ in cand[:cap]]
+    d.size = [s for _, s in cand[:cap]]
+    chain, k = [], 0
+    if cand and cand[0][0] == 0:
+        chain.append(0)
+        while True:
+            want = cand[k][0] + cand[k][1]
+            n = k + 1
+            while n < C and cand[n][0] != want:                      # a linear walk
+                n += 1
+            if n == C:
+                break
+            chain.append(n)
+            k = n
+    L = len(chain)
+    used = cand[chain[-1]][0] + cand[chain[-1]][1] if L else 0
+    isz = [struct.unpack_from("<I", image, cand[k][0] + cand[k][1] - 4)[0] for k in chain]
+    d.written = 0 < L <= max_members
+    d.offsets, d.members, d.coff = [], [], []
+    if d.written:
+        o = 0
+        for k, n in zip(chain, isz):
+            d.offsets.append(o)
+            d.members.append((cand[k][0], cand[k][1], o, n))
+            d.coff.append(cand[k][0])
+            o += n
+        d.offsets.append(o)
+        d.coff.append(used)
+    d.ctl = [C, L, used, d.offsets[-1] if d.written else 0]
+    d.L, d.used, d.chain = L, used, chain
+    return d
+
+
 def voff_to_uoff(coff, uoff, v):
     L = len(coff) - 1
     c, w = v >> 16, v & 0xffff

@@ -86,6 +86,7 @@ static inline uint32_t __shfl_up(uint32_t v, unsigned d, int = 64)
 	const uint32_t r = sim_shfl_idx(v, l >= (int)d ? l - (int)d : l);
 	return r;
 }
+static inline int __shfl_xor(int v, int m, int = 64) { return (int)sim_shfl_idx((uint32_t)v, hipsim::lane() ^ m); }
 static inline int __builtin_amdgcn_readlane(int v, int l) { return (int)sim_shfl_idx((uint32_t)v, l); }
 static inline int __builtin_amdgcn_readfirstlane(int v) { return (int)sim_shfl_idx((uint32_t)v, 0); }
 static inline uint32_t __builtin_amdgcn_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31)); }
@@ -143,7 +144,7 @@ static inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{ x, y }; }
 struct dim3 { unsigned x, y, z; dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) { } };
 typedef struct hipsim_stream *hipStream_t;
 typedef int hipError_t;
-constexpr hipError_t hipSuccess = 0;
+constexpr hipError_t hipSuccess = 0, hipErrorInvalidValue = 1;
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void *p, int v, size_t n, hipStream_t) { memset(p, v, n); return hipSuccess; }
 // the launchers of a kernel file compile and launch nothing: a simulation calls the kernels itself, a workgroup at a time
